@@ -11,7 +11,16 @@ dcol_plan_run over the whole batch: conic assembly + PDIP (pdip_tol 1e-6) + the 
 stream; `kernel_ms` is the HIP-event time of that same timed region on the launch stream / K
 (the per-launch duration of back-to-back launches), so the rooflines come from the same run
 and ms_per_step >= kernel_ms.
-Beside it, `pipeline`: the same steps issued round-robin on --streams (default 2) streams
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what that headline needs and no
+more: set-up, the clock settle, W warm-up steps, the K timed steps, the outputs of the last
+timed step to --dump-outputs DIR when given (DIR/<name>.npy, for comparing two builds output
+for output: the inputs are seeded, the same from run to run), and the result line.  Every
+other section described below -- the pipelined issue, kernel_1m, cost_order, end_to_end, the
+statistics step with the FP64 roofline and the parity check, mixed1m, the ALTRO / drop-in
+sections, the CPU baselines -- is measured with --full only.
+
+Beside it (--full), `pipeline`: the same steps issued round-robin on --streams (default 2) streams
 with their own output buffers, as a pipelined batch service would (the last, partly-filled
 round of one step's waves overlaps the first round of the next) -- an overlap rate, never
 `value`.
@@ -208,6 +217,14 @@ def main():
                     help="timed steps (0.05-2 ms each; enough for the GPU clocks to settle)")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--pairs", type=int, default=100_000, help="pairs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure every other section of the line (pipelined issue, "
+                         "kernel_1m, cost_order, end_to_end, solve statistics + FP64 roofline + parity check, mixed1m, "
+                         "ALTRO / drop-in, CPU baselines); without it the run is the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="poly100k: write what the last timed step computed (the arrays of --timed-outputs) as "
+                         "DIR/<name>.npy, float64; at most 64 MB in all (above that a fixed, seeded sample of the "
+                         "pairs, their indices in pair_index.npy)")
     ap.add_argument("--grad", choices=["fd", "envelope", "implicit"], default="fd",
                     help="fd: the reference's formulation (the headline); envelope / implicit: the closed-form "
                          "and implicit-function modes (DESIGN.md section 3 \"Gradient modes\")")
@@ -257,6 +274,8 @@ def main():
                     help="mixed1m: per-pair arrays + pack_records kernel + out-of-place all-gather instead of "
                          "records written by the solver kernels with the all-gather in place (A/B)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "poly100k":
+        ap.error("--dump-outputs writes the outputs of the poly100k workload's timed steps")
     if args.hw_queues > 0:
         # HIP runtime tunable, read at its initialisation (before any GPU call of this process
         # and inherited by spawned ranks): the pipelined steps run on two caller streams plus
@@ -325,8 +344,8 @@ def main():
     stats_out = ("iters", "status") if args.timed_outputs == "reference" else ()
     out_t = {k: v for k, v in out.items() if k not in stats_out}
     step = plan.bind(pose1, pose2, out_t, grad=args.grad, contact=False, stream=stream, max_iter=args.max_iter)
-    # pipelined issue: S streams, each with its own outputs (poses are read-only, shared)
-    S = max(1, args.streams)
+    # pipelined issue (--full): S streams, each with its own outputs (poses are read-only, shared)
+    S = max(1, args.streams) if args.full else 1
     lane_streams = [stream] + [torch.cuda.Stream(dev) for _ in range(S - 1)]
     lanes = [step] + [plan.bind(pose1, pose2, {k: v for k, v in alloc_outputs(B, dev, want_grad=True,
                                                                             want_contact=False).items()
@@ -371,6 +390,8 @@ def main():
     elapsed = time.perf_counter() - t0
     barrier(dist, wd, "barrier after the timed steps")
     kern_ms = e_start.elapsed_time(e_end) / args.steps
+    # what the last timed step wrote, before anything else runs on these buffers
+    dumped = dump_outputs(args.dump_outputs, out_t, rank) if args.dump_outputs else None
 
     # pipeline: the same K steps round-robin on S streams (an overlap rate, reported beside)
     elapsed_pipe = None
@@ -395,10 +416,11 @@ def main():
     # (kernel_1m right after the timed steps, while the clocks are still at their loaded level:
     # after end_to_end's host-side staging the GPU has idled and re-ramps through the first
     # ~10 ms of launches -- measured 0.44 ms per 1M launch there against 0.36 ms)
-    k1m = kernel_1m(args, eng, ids, tab, dev) if world == 1 and args.kernel_1m else None
+    full = args.full
+    k1m = kernel_1m(args, eng, ids, tab, dev) if full and world == 1 and args.kernel_1m else None
     cord = (cost_order_section(args, eng, ids, s1, s2, p1, p2, dev)
-            if world == 1 and args.cost_order and args.max_iter == 50 else None)
-    e2e = end_to_end(args, eng, ids, s1, s2, p1, p2, pose1, pose2, out_t, step, dev) if world == 1 else None
+            if full and world == 1 and args.cost_order and args.max_iter == 50 else None)
+    e2e = end_to_end(args, eng, ids, s1, s2, p1, p2, pose1, pose2, out_t, step, dev) if full and world == 1 else None
     if dist is not None:
         t = torch.tensor([elapsed, kern_ms, elapsed_pipe or 0.0], device=coll_dev, dtype=torch.float64)
         with guard(wd, "all_reduce of the timings"):
@@ -408,16 +430,19 @@ def main():
     else:
         kern_ms_max = kern_ms
 
-    # one untimed step with every output (the timed ones left status / iters unwritten)
-    plan.bind(pose1, pose2, out, grad=args.grad, contact=False, stream=stream, max_iter=args.max_iter)()
-    sync(dev, wd, "the statistics step")
-    status = out["status"].cpu().numpy()
-    iters = out["iters"].cpu().numpy()
-    alpha = out["alpha"].cpu().numpy()
-    grad = out["grad"].cpu().numpy()
-    # configs[4] on the same ranks (every rank takes part: one all-gather per step)
-    mixed = (mixed_measure(args, world, rank, local, dev, coll_dev, dist, args.mixed_steps, min(args.warmup, 5), wd)
-             if args.mixed_steps > 0 else None)
+    mixed = None
+    if full:
+        # one untimed step with every output (the timed ones left status / iters unwritten)
+        plan.bind(pose1, pose2, out, grad=args.grad, contact=False, stream=stream, max_iter=args.max_iter)()
+        sync(dev, wd, "the statistics step")
+        status = out["status"].cpu().numpy()
+        iters = out["iters"].cpu().numpy()
+        alpha = out["alpha"].cpu().numpy()
+        grad = out["grad"].cpu().numpy()
+        # configs[4] on the same ranks (every rank takes part: one all-gather per step)
+        if args.mixed_steps > 0:
+            mixed = mixed_measure(args, world, rank, local, dev, coll_dev, dist, args.mixed_steps,
+                                  min(args.warmup, 5), wd)
 
     if rank != 0:
         with guard(wd, "destroy_process_group"):
@@ -430,7 +455,6 @@ def main():
     value = total / elapsed
     achieved_gbs = BYTES_PER_PAIR * B / (kern_ms * 1e-3) / 1e9
     traffic = read_traffic(os.path.join(REPO, "profiles"))
-    flops_pair = flops_per_pair(iters[status == 0], args.grad)
     line = {
         "metric": "PDIP proximity+grad pair-solves/sec",
         "value": value,
@@ -451,31 +475,42 @@ def main():
                    "parallelism": f"dp{world} (independent pair shards)"},
         "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic},
-        "roofline_fp64": {"bound": "fp64-valu", "achieved": flops_pair * B / (kern_ms * 1e-3) / 1e12,
-                          "peak": FP64_VECTOR_PEAK_TFS, "unit": "TFLOP/s",
-                          "frac": flops_pair * B / (kern_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFS,
-                          "flops_per_pair": flops_pair,
-                          "flops_source": "op-counting C restatement, profiles/flop_model.json"
-                          if os.path.exists(os.path.join(REPO, "profiles", "flop_model.json")) else "hand model",
-                          **executed_fp64(kern_ms, B, flops_pair)},
         "timing": "value = pairs / ms_per_step of K steps on one stream; kernel_ms = the HIP-event time of that same "
                   "timed region on the launch stream / K (the per-launch duration of the back-to-back launches), the "
                   "rooflines' time base",
         "timed_outputs": ("alpha + gradient (the reference's outputs); status / iters from one untimed step after the "
-                          "timed ones" if stats_out else "alpha, gradient, status, iters"),
-        "pipeline": {"streams": S, "note": "the same K steps issued round-robin on S streams with separate outputs "
-                     "(an overlap rate: one step's last round of waves overlaps the next step's first; not value)",
-                     "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                     "value": (B * world * args.steps / elapsed_pipe) if elapsed_pipe else None,
-                     "ms_per_step": 1e3 * elapsed_pipe / args.steps if elapsed_pipe else None},
+                          "timed ones (--full)" if stats_out else "alpha, gradient, status, iters"),
         "kernel_ms_max_rank": kern_ms_max,
         "settle": settle,
         "world": {"ranks": world, "process_group_size": dist.get_world_size() if dist is not None else 1,
                   "backend": args.backend if dist is not None else None, "devices_visible": ndev},
-        "solve_stats": {"ok_frac": float(np.mean(status == 0)), "iters_mean": float(iters[status == 0].mean()),
-                        "iters_max": int(iters.max()),
-                        "iters_hist": np.bincount(iters, minlength=int(iters.max()) + 1).tolist()},
+        "full": full,
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
+    if not full:    # the headline alone: every other section is --full's
+        print(json.dumps(line), flush=True)
+        if dist is not None:
+            with guard(wd, "destroy_process_group"):
+                dist.destroy_process_group()
+            wd.close()
+        return
+    flops_pair = flops_per_pair(iters[status == 0], args.grad)
+    line["roofline_fp64"] = {"bound": "fp64-valu", "achieved": flops_pair * B / (kern_ms * 1e-3) / 1e12,
+                             "peak": FP64_VECTOR_PEAK_TFS, "unit": "TFLOP/s",
+                             "frac": flops_pair * B / (kern_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFS,
+                             "flops_per_pair": flops_pair,
+                             "flops_source": "op-counting C restatement, profiles/flop_model.json"
+                             if os.path.exists(os.path.join(REPO, "profiles", "flop_model.json")) else "hand model",
+                             **executed_fp64(kern_ms, B, flops_pair)}
+    line["pipeline"] = {"streams": S, "note": "the same K steps issued round-robin on S streams with separate outputs "
+                        "(an overlap rate: one step's last round of waves overlaps the next step's first; not value)",
+                        "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                        "value": (B * world * args.steps / elapsed_pipe) if elapsed_pipe else None,
+                        "ms_per_step": 1e3 * elapsed_pipe / args.steps if elapsed_pipe else None}
+    line["solve_stats"] = {"ok_frac": float(np.mean(status == 0)), "iters_mean": float(iters[status == 0].mean()),
+                           "iters_max": int(iters.max()),
+                           "iters_hist": np.bincount(iters, minlength=int(iters.max()) + 1).tolist()}
     if e2e is not None:
         line["end_to_end"] = e2e
     if k1m is not None:
@@ -550,6 +585,32 @@ def summary(line):
     if "cpu_baseline" in line:
         out["cpu_baseline"] = line["cpu_baseline"]["value"]
     return out
+
+
+DUMP_LIMIT = 64_000_000 - 4096   # bytes of --dump-outputs, all arrays together (64 MB less the .npy headers)
+
+
+def dump_outputs(path, outputs, rank=0, seed=0):
+    """--dump-outputs: the device arrays of `outputs` (pairs along the last axis: alpha [B],
+    grad [12, B], with --timed-outputs all also status / iters [B]) as path/<name>.npy in
+    float64 (rank r > 0: <name>.rank<r>.npy).  Above DUMP_LIMIT bytes in all, the same seeded
+    sample of the pairs from every array, their indices beside them in pair_index.npy.
+    Returns what was written, for the line."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().cpu().numpy().astype(np.float64, copy=False) for k, v in outputs.items()}
+    B = next(iter(host.values())).shape[-1]
+    per_pair = sum(v.nbytes for v in host.values()) // B + 8     # (+ 8: the pair's index)
+    kept = B
+    if per_pair * B > DUMP_LIMIT:
+        kept = DUMP_LIMIT // per_pair
+        sel = np.sort(np.random.default_rng(seed).choice(B, kept, replace=False))
+        host = {k: np.ascontiguousarray(v[..., sel]) for k, v in host.items()}
+        host["pair_index"] = sel.astype(np.float64)
+    suffix = f".rank{rank}" if rank else ""
+    for k, v in host.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), v)
+    return {"dir": path, "arrays": {k: list(v.shape) for k, v in host.items()}, "dtype": "float64",
+            "pairs": int(kept), "of": int(B), "bytes": int(sum(v.nbytes for v in host.values()))}
 
 
 def clock_settle(step, stream, dev, wd, ms):

@@ -77,6 +77,9 @@ def _ensure_built():
     libs.append(os.path.join(PKG, "dcol_amd", "_fastpair.so"))
     if not all(os.path.exists(p) for p in libs):
         subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j8", "-s"], check=True)
+    # the x86 build of the device solver (the emulated-kernel tests; no test skips for want of it)
+    if not os.path.exists(os.path.join(REPO, "tests", "emul", "libdcol_emul.so")):
+        subprocess.run(["make", "-C", os.path.join(REPO, "tests", "emul"), "-j8", "-s"], check=True)
 
 
 _ensure_built()

@@ -19,7 +19,6 @@ import pytest
 from box_shapes import box_pairs, box_table
 from conftest import PKG, REPO, alpha_close, gpu_available, grad_close
 
-EMUL = os.path.join(REPO, "tests", "emul", "libdcol_emul.so")
 LF_BOX = 8
 
 
@@ -34,7 +33,6 @@ def _check_vs_oracle(res, ref, rel_max):
     assert grad_close(res["grad"][ok], ref["grad"][ok]).all()
 
 
-@pytest.mark.skipif(not os.path.exists(EMUL), reason="tests/emul not built")
 def test_emulated_box_rows_asymmetric_match_oracle(monkeypatch):
     from oracle import c_oracle
     from test_emul_golden import emul

@@ -1,7 +1,7 @@
 """x86 build of the device solver (tests/emul, LPP = 1) against the reference's golden
-vectors -- checks the kernel's arithmetic without a GPU.  Skipped unless the emulator has
-been built (`make -C tests/emul -j8`, ~3.5 min of hipcc host compilation, one object per
-(N, NSOC) and row form)."""
+vectors -- checks the kernel's arithmetic without a GPU.  The emulator is built by build()
+(__graft_entry__.py) or, when missing, by tests/conftest.py (`make -C tests/emul -j8`,
+~3.5 min of hipcc host compilation, one object per (N, NSOC) and row form)."""
 import ctypes
 import os
 
@@ -11,7 +11,6 @@ import pytest
 from conftest import REPO, alpha_close, golden_files, grad_close, load_golden
 
 LIB = os.path.join(REPO, "tests", "emul", "libdcol_emul.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="tests/emul not built")
 
 
 def emul(d, tol, flags, max_iter=50):

@@ -11,15 +11,13 @@ default tolerance the implicit one is the closer of the two (measured below agai
 differences of alpha* solved to mu < 1e-11).
 
 CPU: the oracle's restatement (oracle/dcol_oracle.py implicit_gradient) against that true
-derivative and against the emulated kernel (tests/emul, when built).  GPU: the HIP kernel
+derivative and against the emulated kernel (tests/emul).  GPU: the HIP kernel
 against the oracle's restatement at the same iterate.
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import REPO, golden_files, load_golden
+from conftest import golden_files, load_golden
 
 GOLD = {p.split("/")[-1][:-4]: p for p in golden_files()}
 
@@ -72,10 +70,6 @@ def test_oracle_implicit_closer_to_true_derivative_than_reference(name):
     assert e_imp.max() < 1e-3
 
 
-EMUL = os.path.join(REPO, "tests", "emul", "libdcol_emul.so")
-
-
-@pytest.mark.skipif(not os.path.exists(EMUL), reason="tests/emul not built")
 @pytest.mark.parametrize("name", ["scene_quad", "scene_cone", "synthetic_mixed", "edge_cases"])
 def test_emulated_kernel_implicit_matches_oracle(name):
     """The kernel's implicit mode (x86 build, LPP 1) against the oracle's restatement at the

@@ -11,7 +11,7 @@ mkdir -p "$O"
 export TMPDIR=/tmp
 S=tools/gpu_session.sh
 # the headline kernel alone (configs[3], one stream) for PMC passes, and the FP64 counter set
-HB="python3 bench.py --no-cpu --no-altro --check 0 --steps 200 --warmup 100 --streams 1 --mixed-steps 0 --no-kernel-1m"
+HB="python3 bench.py --full --no-cpu --no-altro --check 0 --steps 200 --warmup 100 --streams 1 --mixed-steps 0 --no-kernel-1m"
 F64="SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 GRBM_GUI_ACTIVE"
 M="python3 bench.py --workload mixed1m --no-cpu --no-altro --check 0 --steps 20 --warmup 5"
 case $P in
@@ -22,7 +22,7 @@ case $P in
     OUT=$O $S \
       "tests|900|python3 -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread" \
       "smoke|120|python3 -c 'import __graft_entry__ as g; g.smoke()'" \
-      "bench_default|500|python3 bench.py" \
+      "bench_default|500|python3 bench.py --full" \
       "bench_driver|300|python3 bench.py --gpus 1 --steps 20 --warmup 5" \
       "trace|300|rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- $HB" \
       "trace_mixed|300|rocprofv3 --kernel-trace --stats -f csv -d $O/trace_mixed -o run -- $M" \
@@ -30,7 +30,7 @@ case $P in
       "pmc_write|150|timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -f csv -d $O/pmc_write -o run -- $HB" \
       "pmc_f64|150|timeout -s KILL 120 rocprofv3 --pmc $F64 -f csv -d $O/pmc_f64 -o run -- $HB" \
       "pmc_cycles|150|timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES -f csv -d $O/pmc_cycles -o run -- $HB" \
-      "dp8_gloo|400|python3 bench.py --gpus 8 --backend gloo --no-cpu --steps 50 --warmup 10 --mixed-steps 5 --check 0" ;;
+      "dp8_gloo|400|python3 bench.py --full --gpus 8 --backend gloo --no-cpu --steps 50 --warmup 10 --mixed-steps 5 --check 0" ;;
   classes)    # all 27 mixed classes, 200k pairs each (tools/class_bench.py)
     OUT=$O $S "cls_all27|500|python3 tools/class_bench.py" ;;
   mixed)      # the 1M mixed plan's buckets and a kernel trace of synchronised steps; per-kernel PMC
@@ -54,13 +54,13 @@ case $P in
     OUT=$O ONLY=default,small_fused,small_fused_keyorder,small_nofuse,lat_per_launch $S \
       "sweep|600|python3 tools/shard_bench.py --sweep --buckets --only=default,small_fused,small_fused_keyorder,small_nofuse,lat_per_launch" \
       "trace125k_fused|200|DCOL_SMALL_PLAN_LANES=500000 rocprofv3 --kernel-trace -f csv -d $O/trace125k_fused -o run -- python3 tools/shard_bench.py --worlds 8 --steps 20" \
-      "pmc_f64|150|timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 GRBM_GUI_ACTIVE -f csv -d $O/pmc_f64 -o run -- python3 bench.py --no-cpu --no-altro --check 0 --steps 200 --warmup 100 --streams 1 --mixed-steps 0 --no-kernel-1m" ;;
+      "pmc_f64|150|timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 GRBM_GUI_ACTIVE -f csv -d $O/pmc_f64 -o run -- python3 bench.py --full --no-cpu --no-altro --check 0 --steps 200 --warmup 100 --streams 1 --mixed-steps 0 --no-kernel-1m" ;;
   shards3)    # the packed launch by threshold, shard sizes 1M / N for N = 1 .. 32
     W=1,2,3,4,6,8,12,16,32
     OUT=$O $S \
       "sweep|700|python3 tools/shard_bench.py --sweep --worlds $W --only=default,pack_off,pack_1m,pack_all,pack_keyorder" \
       "trace125k_packed|200|rocprofv3 --kernel-trace -f csv -d $O/trace125k_packed -o run -- python3 tools/shard_bench.py --worlds 8 --steps 20" \
-      "bench|400|python3 bench.py --no-cpu --no-altro --steps 200 --warmup 50" \
+      "bench|400|python3 bench.py --full --no-cpu --no-altro --steps 200 --warmup 50" \
       "pmc_fetch|150|timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/pmc_fetch -o run -- $HB" \
       "pmc_write|150|timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -f csv -d $O/pmc_write -o run -- $HB" \
       "pmc_f64|150|timeout -s KILL 120 rocprofv3 --pmc $F64 -f csv -d $O/pmc_f64 -o run -- $HB" ;;
@@ -74,7 +74,7 @@ case $P in
     OUT=$O $S "tests|1000|python3 -u -m pytest tests -m gpu -q -s --timeout 300 --timeout-method thread ${K:+-k \"$K\"}" ;;
   quick)      # tests named by $K, then a short bench line (every section but the CPU baselines)
     OUT=$O $S "tests|900|python3 -u -m pytest tests -m gpu -q -s --timeout 300 --timeout-method thread -k \"$K\"" \
-      "bench|400|python3 bench.py --no-cpu --steps 100 --warmup 20" ;;
+      "bench|400|python3 bench.py --full --no-cpu --steps 100 --warmup 20" ;;
   shards5)    # the two-family packed launch by threshold; tests named by $K
     W=1,2,3,4,6,8,16,32,64,128,512,4096
     OUT=$O $S \
