@@ -240,6 +240,23 @@ struct dcol_plan {
     bool packed = false;
     bool fused() const { return !segs.empty(); }
     void* d_susp = nullptr;      // DCOL_PLAN_SUSPEND scratch (one allocation for every such launch)
+    // Order-hint state (plan_hints; dcol_device.hpp hint_wave_slot): per stream the plan has
+    // run on, two zero-filled uint8[B] buffers (one allocation), indexed by global slot.  Run k
+    // on the stream reads buf[k % 2] and writes buf[(k + 1) % 2]: within one launch a window's
+    // early waves finish and write before its late waves read, so the two must differ; and
+    // per stream, because dcol_plan_run takes a const plan and runs concurrently on several
+    // streams -- the waves of a window must all see the same bytes.  Created lazily (never
+    // while the stream captures), freed at dcol_plan_destroy; streams past kHintStreams run
+    // without a hint.  mutable + mutex: dcol_plan_run's plan is const.
+    static constexpr int kHintStreams = 8;
+    struct HintState {
+        hipStream_t stream = nullptr;
+        uint8_t* buf = nullptr;   // [2][B]
+        uint64_t runs = 0;
+    };
+    mutable std::mutex hint_mu;
+    mutable HintState hints[kHintStreams];
+    mutable int n_hints = 0;
     ~dcol_plan() {
         if (fork) (void)hipEventDestroy(fork);
         for (hipEvent_t& e : join)
@@ -953,6 +970,11 @@ int dcol_plan_destroy(dcol_plan* p) {
         if (p->d_segs) (void)hipFree(p->d_segs);
         if (p->d_susp) (void)hipFree(p->d_susp);
     }
+    if (p->table && p->n_hints > 0) {
+        DeviceGuard g(p->table->device);
+        for (int i = 0; i < p->n_hints; ++i)
+            if (p->hints[i].buf) (void)hipFree(p->hints[i].buf);
+    }
     delete p;
     return DCOL_SUCCESS;
 }
@@ -1013,11 +1035,65 @@ int dcol_plan_bucket(const dcol_plan* p, int32_t i, int32_t info[8], int64_t* pa
 }  // extern "C"
 
 namespace {
+// waves per order-hint window (DCOL_HINT_WAVES, 1..kHintWavesMax; A/B runs)
+int hint_waves() {
+    static const int ww = [] {
+        const char* e = std::getenv("DCOL_HINT_WAVES");
+        const int v = e ? std::atoi(e) : kHintWavesDefault;
+        return std::min(std::max(v, 1), kHintWavesMax);
+    }();
+    return ww;
+}
+
+// The order-hint buffers of this run of p on st: *rd the previous run's iteration counts on
+// this stream (zeros before the first), *wr where this run leaves its own.  false: the run
+// goes without a hint (DCOL_NO_ORDER_HINT=1; a plan with no hinted launch; a first run on a
+// capturing stream; more than kHintStreams streams; no memory).  A run captured into a graph
+// keeps the pair it was captured with at every replay: it reads one buffer and writes the
+// other each time, a frozen, consistent order.
+bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t** wr) {
+    static const bool off = [] {
+        const char* e = std::getenv("DCOL_NO_ORDER_HINT");
+        return e && *e && *e != '0';
+    }();
+    if (off || p->fused() || p->B >= (int64_t)1 << 31) return false;
+    bool any = false;
+    for (const Launch& L : p->launches) any = any || (L.kind == 0 && !L.susp);
+    if (!any) return false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (capturing) (void)hipGetLastError();
+    std::lock_guard<std::mutex> lk(p->hint_mu);
+    dcol_plan::HintState* S = nullptr;
+    for (int i = 0; i < p->n_hints && !S; ++i)
+        if (p->hints[i].stream == st) S = &p->hints[i];
+    if (!S) {
+        if (capturing || p->n_hints >= dcol_plan::kHintStreams) return false;
+        uint8_t* b = nullptr;
+        if (hipMalloc(&b, 2 * (size_t)p->B) != hipSuccess || hipMemsetAsync(b, 0, 2 * (size_t)p->B, st) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b) (void)hipFree(b);
+            return false;
+        }
+        S = &p->hints[p->n_hints++];
+        S->stream = st;
+        S->buf = b;
+        S->runs = 0;
+    }
+    const uint64_t k = S->runs & 1;
+    *rd = S->buf + k * (size_t)p->B;
+    *wr = S->buf + (k ^ 1) * (size_t)p->B;
+    if (!capturing) ++S->runs;
+    return true;
+}
+
 // dcol_plan_run with an optional record output (rec: [B][DCOL_REC], written by the solver
 // epilogues; then alpha / grad / iters / status may be NULL)
+// hint: the run may use and leave an order hint (not dcol_prox_batch_host's plan, which
+// runs once, nor dcol_prox_pair's one-pair plans, which have nothing to order)
 int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, double tol, int32_t max_iter,
                  int32_t flags, double* alpha, double* contact, double* grad, int32_t* iters, int32_t* status,
-                 double* rec, void* stream, bool yield = true) {
+                 double* rec, void* stream, bool yield = true, bool hint = true) {
     if (!p) return fail(DCOL_ERR_ARG, "dcol_plan_run: NULL plan");
     // (the pair call's own launch path keeps it).  A small plan keeps it too -- unless it is
     // launched on the null stream: the server runs on a blocking stream (CU-masked streams
@@ -1064,6 +1140,10 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     const int fdonly = (flags & (DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)) ? 0 : LF_FDONLY;
     const bool fan = p->lanes > 1 && p->fork;
     hipError_t e = hipSuccess;
+    // (before the fork: the side streams' launches then follow a new state's zero fill)
+    const uint8_t* hint_r = nullptr;
+    uint8_t* hint_w = nullptr;
+    const bool hinted = hint && plan_hints(p, st, &hint_r, &hint_w);
     if (fan) {
         e = hipEventRecord(p->fork, st);
         for (int l = 1; e == hipSuccess && l < p->lanes; ++l) e = hipStreamWaitEvent(t->side[l - 1], p->fork, 0);
@@ -1093,7 +1173,14 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
         } else {
             const int split = (L.oe > 0 && L.lpp == 2 && split_enabled() && split_built(L.N, L.nsoc, L.omax, L.oe))
                                   ? LF_SPLIT : 0;
-            e = launch_variant(L.N, L.nsoc, L.omax, L.lpp, L.flags() | fdonly | split, a, ls, L.oe);
+            KArgs b = a;
+            if (hinted) {   // every solve bucket of the "one bucket" and "buckets" forms
+                b.hint_r = hint_r;
+                b.hint_w = hint_w;
+                b.hint_ww = hint_waves();
+                b.hint_wins = hint_windows(L.n, L.lpp, b.hint_ww);
+            }
+            e = launch_variant(L.N, L.nsoc, L.omax, L.lpp, L.flags() | fdonly | split, b, ls, L.oe);
         }
         if (e != hipSuccess) break;
     }
@@ -1345,7 +1432,7 @@ int dcol_prox_pair(const dcol_table* tc, int32_t s1, int32_t s2, const double* p
     // row-partitioned x polytope kernels 4-5 % of throughput; the server serves the latency
     // path now.)
     int rc = plan_run_rec(plan, d->pose1, d->pose2, tol, max_iter, flags & ~DCOL_CASE4, &d->alpha, d->contact,
-                          d->grad, &d->iters, &d->status, nullptr, t->pair_stream, false);
+                          d->grad, &d->iters, &d->status, nullptr, t->pair_stream, false, false);
     if (rc != DCOL_SUCCESS) return rc;
     ++t->n_launched;
     const hipError_t e = hipStreamSynchronize(t->pair_stream);
@@ -1548,7 +1635,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     if (e == hipSuccess) e = hipMemcpy(ib, ids, sizeof(int32_t) * 3 * B, hipMemcpyHostToDevice);
     if (e == hipSuccess && segb) e = hipMemcpy(dsg, p.segs.data(), segb, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(DCOL_ERR_HIP, std::string("dcol_prox_batch_host H2D: ") + hipGetErrorString(e));
-    rc = dcol_plan_run(&p, dp1, dp2, tol, max_iter, flags, dal, dct, dgr, dit, dst, nullptr);
+    rc = plan_run_rec(&p, dp1, dp2, tol, max_iter, flags, dal, dct, dgr, dit, dst, nullptr, nullptr, true, false);
     if (rc != DCOL_SUCCESS) return rc;
     e = hipMemcpy(outd, dal, sizeof(double) * nout, hipMemcpyDeviceToHost);   // synchronises
     if (e == hipSuccess) e = hipMemcpy(ids + 3 * B, dit, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost);

@@ -182,6 +182,16 @@ struct KArgs {
     int32_t* susp_pi;                   // [susp_cap] pair index (slot index into perm space)
     double* susp_state;                 // [fields][susp_cap]: it, x[N], then (s, z, r) per lane row
     int64_t susp_cap;
+    // Window-local order hint (hint_wave_slot below; dcol_capi.cpp HintState): the iteration
+    // counts of the (plan, stream)'s previous run, one byte per launch slot, indexed by the
+    // global slot slot0 + slot.  hint_r is read by the prologue, hint_w written by the
+    // epilogue (the other buffer of the pair); both nullptr and hint_wins 0: no hint, the
+    // launch maps thread -> slot linearly.  hint_wins: windows of the launch padded to a
+    // multiple of 8 (the grid is hint_wins * hint_ww waves); hint_ww: waves per window.
+    const uint8_t* __restrict__ hint_r = nullptr;
+    uint8_t* __restrict__ hint_w = nullptr;
+    int32_t hint_wins = 0;
+    int32_t hint_ww = 0;
 #ifdef DCOL_STAMPS
     unsigned long long* stamps = nullptr;   // diagnostic build only (tools/stamp_probe.hip, the pair
                                             // server of lib_stamps): [B][16]; nullptr: none
@@ -2390,7 +2400,8 @@ DCOL_HD void launder(P& p) {
 // compiled in, so its register pressure never shapes the FD path (variants.py BOX_FD)
 template <int N, int NSOC, int OMAX, int LPP, bool FULL = false, bool BALL = false, bool CONE = false, int OE = 0,
           int MODE = 0, bool GLDS = false, bool BOX = false, bool FDONLY = false, bool SPLIT = false>
-DCOL_HD void solve_one(const KArgs& A, int64_t pi, int q, int64_t ci = -1, int k1o = -1, int k2o = -1) {
+DCOL_HD void solve_one(const KArgs& A, int64_t pi, int q, int64_t ci = -1, int k1o = -1, int k2o = -1,
+                       int32_t hs = -1) {
     DCOL_STAMP(A, pi, q, 0);
     const int64_t B = A.B;
     // k1o / k2o >= 0: the shape ids given (the one-pair server reads them with its request)
@@ -2544,6 +2555,9 @@ DCOL_HD void solve_one(const KArgs& A, int64_t pi, int q, int64_t ci = -1, int k
     if (A.alpha) A.alpha[pi] = al;
     if (A.iters) A.iters[pi] = it;
     if (A.status) A.status[pi] = st;
+    // the order hint of this (plan, stream)'s next run: the pair's iteration count at its
+    // launch slot hs (prox_kernel; -1: a launch form without hints)
+    if (hs >= 0 && A.hint_w) A.hint_w[A.slot0 + hs] = (uint8_t)(it < 255 ? it : 255);
     if ((A.flags & F_CONTACT) && A.contact) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) A.contact[c * B + pi] = ok ? P.x[c] : nan;
@@ -2584,15 +2598,136 @@ constexpr bool kGlds = false;
 #else
 constexpr bool kGlds = true;
 #endif
+// ------------------------------------------------------------------------------------
+// Window-local order hint: which lane group of which wave solves which slot.
+//
+// A launch's slots are cut into windows of ww waves' worth (ww * 64 / LPP consecutive
+// slots).  Inside a window the slots are ordered by the stable descending counting sort of
+// their hint bytes (the pair's iteration count of the previous run, clamped to 0..63), and
+// the window's wave of rank r takes positions [r * 64 / LPP, (r + 1) * 64 / LPP) of that
+// order: pairs of similar cost share a wave, the slowest wave has rank 0.  Equal hints (the
+// zero-filled first run) give the identity, i.e. contiguous slots per wave.  Any bytes give
+// a permutation of the window's slots, so every slot is solved exactly once as long as the
+// window's waves read the same bytes (dcol_capi.cpp: one buffer pair per plan and stream).
+// ------------------------------------------------------------------------------------
+constexpr int kHintWavesMax = 8;   // waves per window, at most (the keys of a window sit in registers)
+constexpr int kHintWavesDefault = 4;   // measured 4 / 8 / 16 on configs[3]: DESIGN.md section 5
+DCOL_HD int hint_key(uint8_t h) { return h > 63 ? 63 : (int)h; }
+// The rule in scalar form: the position of slot i of a window of len slots with hint bytes
+// h[0 .. len) in the window's order (tests/emul_hint checks it; hint_wave_slot is its wave form).
+DCOL_HD int hint_position(const uint8_t* h, int len, int i) {
+    const int k = hint_key(h[i]);
+    int p = 0;
+    for (int j = 0; j < len; ++j) {
+        const int kj = hint_key(h[j]);
+        p += (kj > k || (kj == k && j < i)) ? 1 : 0;
+    }
+    return p;
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The launch slot of this lane's group under the hint, or -1 if the group has none (a
+// phantom window or wave of the padded grid, the ragged end).  Called by every lane of the
+// wave (ballots); the lanes of a group get the same answer.  Wave w of the launch is rank
+// w / hint_wins of window w % hint_wins: every window's slowest wave is dispatched first,
+// and with hint_wins a multiple of 8 a window's waves share blockIdx % 8.
+// Lane K of the wave doubles as the counter of key K (64 lanes, 64 keys): per chunk of 64
+// slots six ballots of the key bits give each lane both the lanes holding its own key and
+// the lanes holding key K.
+template <int LPP>
+__device__ __forceinline__ int32_t hint_wave_slot(const KArgs& A) {
+    constexpr int PPW = 64 / LPP;   // slots per wave
+    constexpr int JMAX = (kHintWavesMax * PPW + 63) / 64;   // chunks of 64 slots per window, at most
+    __shared__ uint16_t order[kSolveBlock / 64][PPW];   // this wave's share of the window's order
+    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
+    const uint32_t w = blockIdx.x * (uint32_t)(kSolveBlock / 64) + (uint32_t)wv;
+    const int rank = (int)(w / (uint32_t)A.hint_wins);
+    const int64_t win = w % (uint32_t)A.hint_wins;
+    const int ws = A.hint_ww * PPW;   // slots per window
+    const int64_t base = win * ws;
+    if (rank >= A.hint_ww || base >= A.n) return -1;   // (wave-uniform)
+    const int len = (int)(A.n - base < ws ? A.n - base : ws);
+    const uint8_t* __restrict__ h = A.hint_r + A.slot0 + base;
+    // the window's keys, one load per chunk, all in flight together; -1: past the window's end
+    int key[JMAX];
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) {
+        const int i = j * 64 + lane;
+        key[j] = i < len ? hint_key(h[i]) : -1;
+    }
+    // pass 1: lane K counts the window's slots of key K, chunk by chunk
+    int cntc[JMAX];
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) {
+        cntc[j] = 0;
+        if (j * 64 < len) {   // (wave-uniform)
+            unsigned long long ofk = __builtin_amdgcn_ballot_w64(key[j] >= 0);
+#pragma unroll
+            for (int b = 0; b < 6; ++b) {
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(((key[j] >> b) & 1) != 0);
+                ofk &= ((lane >> b) & 1) ? m : ~m;
+            }
+            cntc[j] = __popcll(ofk);
+            cnt += cntc[j];
+        }
+    }
+    // descending order: key K's run starts after every larger key's (suffix sum over lanes)
+    int start = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_down(start, d, 64);
+        if (lane + d < 64) start += o;
+    }
+    start -= cnt;
+    // pass 2: each slot's position = its key's run start + the equal keys before it
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int lo = rank * PPW;
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) {
+        if (j * 64 < len) {
+            const bool v = key[j] >= 0;
+            unsigned long long mine = __builtin_amdgcn_ballot_w64(v);
+#pragma unroll
+            for (int b = 0; b < 6; ++b) {
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(((key[j] >> b) & 1) != 0);
+                mine &= ((key[j] >> b) & 1) ? m : ~m;
+            }
+            const int p = __shfl(start, key[j] & 63, 64) + __popcll(mine & below) - lo;
+            if (v && p >= 0 && p < PPW) order[wv][p] = (uint16_t)(j * 64 + lane);
+            start += cntc[j];   // key K's slots of this chunk are placed
+        }
+    }
+    // the wave's own writes, read back by its other lanes: LDS operations of one wave
+    // execute in order, so only the compiler has to keep them so (no workgroup barrier)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const int g = lane / LPP;
+    if (lo + g >= len) return -1;
+    return (int32_t)(base + order[wv][g]);
+}
+#endif
+
 template <int N, int NSOC, int OMAX, int LPP, int WPS, int FL, int OE = 0>
 __global__ void __launch_bounds__(kSolveBlock, WPS % 10) prox_kernel(KArgs A) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t slot = t / LPP;
+    int64_t slot = t / LPP;
     const int q = (int)(t % LPP);
+    int32_t hs = -1;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr ((FL & 16) == 0) {   // (a suspend / resume main launch carries no hint)
+        if (A.hint_wins > 0) {
+            hs = hint_wave_slot<LPP>(A);
+            if (hs < 0) return;
+            slot = hs;
+        }
+    }
+#endif
     if (slot >= A.n) return;
     const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
     solve_one<N, NSOC, OMAX, LPP, (FL & 1) != 0, (FL & 2) != 0, (FL & 4) != 0, OE, (FL & 16) ? 1 : 0,
-              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0>(A, pi, q);
+              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0>(A, pi, q, -1, -1, -1, hs);
 }
 
 // The resume launch of a suspend / resume pair: one lane group per continuation entry;

@@ -22,7 +22,7 @@ namespace dcol {
 #define DCOL_PCASE(NN, NS, OM, LP, WP, FL, OEE)                                                    \
     if constexpr (NN == DCOL_TU_N && NS == DCOL_TU_NS && DCOL_TU_FLOK(FL))                         \
         if (omax == OM && oe == OEE && lpp == LP && (FL & flags) == FL && (wps == 0 || wps == WP % 10)) { \
-            const int64_t grid = (args.n * LP + kBlock - 1) / kBlock;                              \
+            const int64_t grid = solve_grid(args, LP);                                             \
             hipLaunchKernelGGL((prox_kernel<NN, NS, OM, LP, WP, FL, OEE>), dim3(grid), dim3(kBlock), 0, stream, args); \
             return hipGetLastError();                                                              \
         }

@@ -10,6 +10,21 @@ enum : int { LF_FULL = 1, LF_BALL = 2, LF_CONE = 4, LF_BOX = 8, LF_SPLIT = 32, L
 constexpr int kBlock = kSolveBlock;   // threads per workgroup of the solve kernel
 constexpr int kSideStreams = 7;   // capacity of the extra streams for concurrent variant launches
                                   // (dcol_capi.cpp side_streams(): 3 by default, DCOL_SIDE_STREAMS)
+// Grid of a prox_kernel launch: n * lpp threads mapped linearly, or -- with an order hint
+// (KArgs hint_wins > 0, dcol_device.hpp hint_wave_slot) -- hint_ww waves for each of the
+// hint_wins windows, phantom ones included (they exit at once)
+inline int64_t solve_grid(const KArgs& a, int lpp) {
+    constexpr int wpb = kBlock / 64;   // waves per workgroup
+    if (a.hint_wins > 0) return ((int64_t)a.hint_wins * a.hint_ww + wpb - 1) / wpb;
+    return (a.n * lpp + kBlock - 1) / kBlock;
+}
+// windows of a launch of n slots at ww waves per window, padded to a multiple of 8: a window's
+// waves then carry the same blockIdx % 8 (the hardware deals workgroups to its 8 XCDs round
+// robin, so they share an L2).  A speed choice only.
+inline int32_t hint_windows(int64_t n, int lpp, int ww) {
+    const int64_t ws = (int64_t)ww * (64 / lpp);
+    return (int32_t)(((n + ws - 1) / ws + 7) / 8 * 8);
+}
 hipError_t launch_n4(int nsoc, int omax, int lpp, int flags, const KArgs& args, hipStream_t stream);
 hipError_t launch_n5(int nsoc, int omax, int lpp, int flags, const KArgs& args, hipStream_t stream);
 hipError_t launch_n6(int nsoc, int omax, int lpp, int flags, const KArgs& args, hipStream_t stream);

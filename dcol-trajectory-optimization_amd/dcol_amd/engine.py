@@ -246,9 +246,13 @@ def cost_order(iters) -> np.ndarray:
     pairing solves the same pairs with bitwise the same results.  For a trajectory optimiser
     (the same pairs at slowly changing poses) re-list once from a solve's `iters` and keep
     the order -- measured on configs[3] at drifting poses: bench.py `cost_order`,
-    tools/order_probe.py.  The plan itself cannot reorder slots for free: a permutation read
-    through an index array turns the coalesced pose / output accesses into gathers and
-    scatters, which cost more than the order saves."""
+    tools/order_probe.py.  A plan run repeatedly on a stream does a window-local form of
+    this by itself (the order hint of dcol_plan_run, include/dcol.h: pairs regrouped by
+    their last counts inside windows of a few hundred consecutive pairs, whose pose and
+    output rows the window's waves share); a permutation of the whole batch read through an
+    index array turns the coalesced pose / output accesses into gathers and scatters, which
+    cost more than the order saves.  The full re-listing here removes
+    the idle lanes the windows leave."""
     it = np.asarray(iters).reshape(-1)
     return np.argsort(-it.astype(np.int64), kind="stable")
 

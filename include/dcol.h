@@ -184,8 +184,24 @@ int dcol_plan_suspended(const dcol_plan* plan, int64_t* n);
  *   iters        : [B]      Newton steps taken (may be NULL)
  *   status       : [B]      enum dcol_status (may be NULL)
  * tol is pdip_tol (reference default 1e-6); max_iter the iteration cap (reference: 50).
- * Asynchronous on `stream` (a hipStream_t, NULL = default stream); no allocation and no
- * synchronisation, so the call can be captured into a hipGraph.                        */
+ * Asynchronous on `stream` (a hipStream_t, NULL = default stream); no synchronisation, and
+ * no allocation while the stream is capturing, so the call can be captured into a hipGraph.
+ *
+ * Order hint.  A plan of the DCOL_FORM_BUCKETS form keeps, per stream it has been run on
+ * (up to 8; further streams run without), two bytes per pair of device memory: each run
+ * leaves every pair's iteration count there, and the stream's next run uses it to put
+ * pairs of similar cost -- inside windows of a few hundred consecutive pairs -- into the
+ * same wave, the slowest wave first.  Only which lane group solves which pair changes; the
+ * outputs are bitwise those of a run without the hint (DCOL_NO_ORDER_HINT=1; the window is
+ * DCOL_HINT_WAVES waves, 1..8, default 4).  The state is allocated by the first run on a stream
+ * that is not capturing (one hipMalloc, zero-filled on that stream) and freed by
+ * dcol_plan_destroy, so destroy the plan after its runs have completed, as before.  The
+ * runs of one plan on one stream must be issued by one thread at a time; different
+ * streams are independent.
+ * Capture: a run captured into a hipGraph keeps the two buffers it was captured with, so
+ * every replay uses the same, frozen order and stays consistent.  A first run on a
+ * capturing stream gets no hint.  Do not replay such a graph concurrently with other runs
+ * of the plan on the stream it was captured from: they would write the bytes it reads.  */
 int dcol_plan_run(const dcol_plan* plan, const double* pose1, const double* pose2, double tol,
                   int32_t max_iter, int32_t flags, double* alpha, double* contact, double* grad,
                   int32_t* iters, int32_t* status, void* stream);
