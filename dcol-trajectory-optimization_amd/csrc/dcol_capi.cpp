@@ -4,8 +4,9 @@
 //    of orthant-row descriptors (DevRow), uploaded once to HBM.  This is the static part of
 //    problem_matrices() (primitives/problem_matrices.py:4-209): the per-type constant rows;
 //    the pose-dependent part (DCM, rotation, h) runs inside the kernel.
-//  * dcol_plan_create: classifies each pair (combine_problem_matrices.py:3-70 cases 1-3 vs
-//    the unsupported case 4) and buckets pairs by kernel variant (N, NSOC, OMAX).
+//  * dcol_plan_create: the plan's layout (dcol_plan.hpp plan_layout: each pair classified --
+//    combine_problem_matrices.py:3-70 cases 1-3 vs the unsupported case 4 -- and bucketed by
+//    kernel variant (N, NSOC, OMAX)) and its device state.
 //  * dcol_plan_run: one kernel launch per non-empty bucket, asynchronous on the caller's
 //    stream, no allocation (graph-capturable) -- or, for a small plan that mixes variants,
 //    ONE fused launch covering every bucket (dcol_kernels_fused.hip).
@@ -22,7 +23,6 @@
 #include <mutex>
 #include <string>
 #include <thread>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -30,6 +30,7 @@
 #include "dcol_device.hpp"
 #include "dcol_host.hpp"
 #include "dcol_launch.hpp"
+#include "dcol_plan.hpp"
 
 using namespace dcol;
 using namespace dcol_host;
@@ -70,31 +71,15 @@ DeviceSide& device_side(int dev) {
     static DeviceSide g[64];
     return g[dev & 63];
 }
-// side streams per device: 3 (with the caller's stream, 4 = HIP's default hardware queues),
-// DCOL_SIDE_STREAMS=<1..7> for A/B runs (then raise GPU_MAX_HW_QUEUES to match)
-int side_streams() {
-    static const int n = [] {
-        const char* e = std::getenv("DCOL_SIDE_STREAMS");
-        const int v = e ? std::atoi(e) : 3;
-        return v < 1 ? 1 : (v > kSideStreams ? kSideStreams : v);
-    }();
-    return n;
+// The plan policy's knobs (dcol_plan.hpp PlanPolicy), read from the environment once per
+// process, at their first use
+const PlanPolicy& plan_policy() {
+    static const PlanPolicy pol = PlanPolicy::from_env();
+    return pol;
 }
-// side streams a plan that fills the GPU fans out over: 2 -- three buckets in flight with the
-// caller's stream.  Fewer concurrent buckets finish a large mixed step sooner: the
-// one-wave-per-SIMD kernels (400-500 registers) need a whole SIMD's register file and wait
-// behind co-running buckets' waves when four run at once (1M mixed plan, synchronised
-// steps: 0.87 ms at 2 against 0.94 ms at 3 and 1).  A small plan (its
-// buckets cannot fill the GPU, each runs its latency configuration) keeps every side
-// stream.  DCOL_SIDE_STREAMS_LARGE=<1..side_streams()> for A/B runs.
-int large_side_streams() {
-    static const int n = [] {
-        const char* e = std::getenv("DCOL_SIDE_STREAMS_LARGE");
-        const int v = e ? std::atoi(e) : 2;
-        return v < 1 ? 1 : (v > side_streams() ? side_streams() : v);
-    }();
-    return n;
-}
+// side streams per device, and those a plan that fills the GPU fans out over
+int side_streams() { return plan_policy().side_streams; }
+int large_side_streams() { return plan_policy().side_streams_large; }
 
 // dcol_prox_pair's one-pair server: how long (us) it stays resident without a request
 // (DCOL_PAIR_SERVER_IDLE_US, default 1000); DCOL_PAIR_SERVER=0: no server, one launch per
@@ -198,10 +183,10 @@ struct dcol_table {
     double srv_us = 0.0, srv_cycles = 0.0;
 };
 
-struct Launch {
-    int kind;       // 0 = solve, 1 = reject
-    int N, nsoc, omax, lpp;
-    int oe = 0;          // row-partitioned bucket (extra-row slots; 0: dense-row kernels)
+// A bucket of the plan's layout with its device state
+struct Launch : Bucket {
+    Launch() = default;
+    Launch(const Bucket& b) : Bucket(b) {}
     // suspend / resume pair (DCOL_PLAN_SUSPEND): continuation entries, their buffers
     bool susp = false;
     int susp_fields = 0;
@@ -209,14 +194,6 @@ struct Launch {
     int32_t* d_susp_count = nullptr;
     int32_t* d_susp_pi = nullptr;
     double* d_susp_state = nullptr;
-    bool full = false;   // every pair has o == omax: the padding-free kernel (DCOL_FULL_VARIANTS) if built
-    bool ball = false;   // every SOC block is a ball block: the structured kernel (DCOL_BALL_VARIANTS) if built
-    bool cone = false;   // every SOC block is a cone block (N = 4): DCOL_CONE_VARIANTS if built
-    bool box = false;    // every pair is box x box (DevShape::boxp; with full): DCOL_BOX_VARIANTS if built
-    int flags() const { return (full ? LF_FULL : 0) | (ball ? LF_BALL : 0) | (cone ? LF_CONE : 0) | (box ? LF_BOX : 0); }
-    int32_t code;   // reject status
-    int64_t slot0, n;
-    int lane = 0;   // 0 = caller's stream, 1..kSideStreams = table side stream
 };
 
 struct dcol_plan {
@@ -226,19 +203,11 @@ struct dcol_plan {
     int32_t* d_s2 = nullptr;
     int32_t* d_perm = nullptr;   // nullptr when the whole batch is one variant
     bool owns = false;           // device arrays owned (false: views into table staging)
-    std::vector<Launch> launches;
-    int lanes = 1;               // streams the launches are spread over (1 = serial)
-    bool small = false;          // the plan cannot fill the GPU (bucket_pairs: small_plan)
-    std::vector<int> issue;      // launch issue order (assign_lanes: longest first); empty = as built
+    PlanLayout lay;              // what the plan launches (dcol_plan.hpp plan_layout)
+    std::vector<Launch> launches;   // lay.buckets, each with its device state
     hipEvent_t fork = nullptr;   // recorded on the caller's stream, awaited by the side streams
     hipEvent_t join[kSideStreams] = {};
-    // fused launch (small mixed plans) or packed launch (mid-size plans, packed = true): one
-    // segment per solve bucket, in descending per-pair cost (plan_segments)
-    std::vector<FusedSeg> segs;
-    FusedSeg* d_segs = nullptr;
-    int64_t fused_blocks = 0;
-    bool packed = false;
-    bool fused() const { return !segs.empty(); }
+    FusedSeg* d_segs = nullptr;  // lay.segs on the device
     void* d_susp = nullptr;      // DCOL_PLAN_SUSPEND scratch (one allocation for every such launch)
     // Order-hint state (plan_hints; dcol_device.hpp hint_wave_slot): per stream the plan has
     // run on, two zero-filled uint8[B] buffers (one allocation), indexed by global slot.  Run k
@@ -287,8 +256,8 @@ bool stop_pair_server(dcol_table* t, int timeout_ms) {
     return true;
 }
 
-// A batch launch that can fill `device` (a plan that is not small: bucket_pairs) asks every
-// resident pair server there to leave (it does after
+// A batch launch that can fill `device` (a plan that is not small: PlanLayout::small) asks
+// every resident pair server there to leave (it does after
 // the request in hand, at its next poll), without waiting: a kernel resident beside a batch
 // plan slowed the plan by 1.3-2x depending on the server stream's kind and the number of
 // hardware queues (tools/server_tax.py, profiles/r05_d/, r05_e/), so the latency path gives
@@ -460,245 +429,6 @@ int dcol_pair_dims(const dcol_table* t, int32_t s1, int32_t s2, int32_t* m, int3
 }  // extern "C"
 
 namespace {
-void assign_lanes(dcol_plan* p);
-
-// DCOL_SMALL_FANOUT=1: a small plan the fused kernel cannot take fans its latency-configured
-// buckets out (the behaviour before the packed launch; A/B runs)
-bool small_fanout() {
-    static const bool on = std::getenv("DCOL_SMALL_FANOUT") != nullptr;
-    return on;
-}
-
-// DCOL_NO_BALL=1: ball-SOC pairs run the dense kernels too (A/B runs, tests)
-bool ball_disabled() {
-    static const bool off = std::getenv("DCOL_NO_BALL") != nullptr;
-    return off;
-}
-// DCOL_NO_BOX=1: box x box pairs run the padding-free dense-row kernel (A/B runs, tests)
-bool box_disabled() {
-    static const bool off = std::getenv("DCOL_NO_BOX") != nullptr;
-    return off;
-}
-
-// DCOL_NO_CONE=1: cone-SOC pairs run the dense (padded) kernels (A/B runs, tests)
-bool cone_disabled() {
-    static const bool off = std::getenv("DCOL_NO_CONE") != nullptr;
-    return off;
-}
-
-// Lanes below which a plan counts as small -- it cannot fill the GPU: every bucket takes its
-// latency configuration and a mixed plan runs as one fused launch (bucket_pairs, plan_fuse).
-// 64 x SIMDs (one wave per SIMD); DCOL_SMALL_PLAN_LANES=<n> for A/B runs.
-int64_t small_lanes(const dcol_table* t) {
-    static const int64_t v = [] {
-        const char* e = std::getenv("DCOL_SMALL_PLAN_LANES");
-        return e ? std::atoll(e) : 0LL;
-    }();
-    return v > 0 ? v : 64LL * t->simds;
-}
-
-// A launch too small to fill the GPU runs the configuration with the shortest per-pair
-// latency: fewest orthant slots per lane (omax / lpp), over the pair's bucket and the larger
-// buckets up to twice its rows (a tight bucket compiled only with LPP 2 -- 6 or 10 rows --
-// loses to the next bucket's 8-lane groups), fewer rows on ties.
-void latency_config(Launch& L) {
-    if (L.oe > 0) {   // row-partitioned bucket: its largest compiled LPP
-        L.lpp = part_lpp(L.N, L.nsoc, L.omax, L.oe, true);
-        return;
-    }
-    const int fl = L.ball ? 2 : (L.cone ? 4 : 0);
-    int best_o = L.omax, best_l = max_lpp(L.N, L.nsoc, L.omax, fl);
-    for (const int om : buckets().at({L.N, L.nsoc})) {
-        if (om <= L.omax || om > 2 * L.omax) continue;
-        const int l = max_lpp(L.N, L.nsoc, om, fl);
-        if (om * best_l < best_o * l) {   // om / l < best_o / best_l
-            best_o = om;
-            best_l = l;
-        }
-    }
-    if (best_o != L.omax) L.full = false;   // the pairs no longer fill the bucket
-    L.omax = best_o;
-    L.lpp = best_l;
-}
-
-// Classify + bucket (counting sort by variant key).  Fills p->launches and the slot->pair
-// permutation; returns DCOL_SUCCESS or an error.
-// O(B): each distinct (shape1, shape2) is classified once (a dense S x S cache when S^2 is
-// at most 4M cells and small against B, else a hash map), then a stable counting sort by
-// group, groups in key order.
-// fused_part: a row-partitioned bucket is used only where the fused small-plan kernel has
-// its case (the retry of a small plan that would otherwise lose its single fused launch;
-// the other pairs take the dense-row kernels, which the fused kernel covers)
-// lat_part: a row-partitioned bucket compiled only for one lane per pair is not used (the
-// retry of a plan that cannot fill the GPU: one lane working through every row of the pair
-// is slower than the dense rows' multi-lane groups -- polygon x box, 1,000 pairs: 84 us in
-// the (11, 5) one-lane bucket against 52 us in the dense (6, 1, 12) four-lane kernel)
-// small_out: set to whether the plan cannot fill the GPU (its buckets took their latency
-// configurations); force_large: bucket as a plan that fills it (throughput configurations:
-// the packed launch of a small plan the fused kernel cannot take, bucket_and_fuse)
-int bucket_pairs(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, dcol_plan* p,
-                 std::vector<int32_t>& perm, bool case4, bool fused_part = false, bool lat_part = false,
-                 bool* small_out = nullptr, bool force_large = false) {
-    const int32_t ns = (int32_t)t->shapes.size();
-    // kind, N, nsoc, omax, lpp, ball (SOC blocks all balls: no cone), code, oe (row partition)
-    using Key = std::tuple<int, int, int, int, int, int, int, int>;
-    struct Group {
-        Key key;
-        bool full = true;   // every pair class of the group has o == omax
-        int64_t n = 0, at = 0;
-    };
-    std::map<Key, int32_t> gid_of_key;
-    std::vector<Group> groups;
-    auto classify_pair = [&](int32_t i1, int32_t i2) -> int32_t {
-        const DevShape& a = t->shapes[i1];
-        const DevShape& b = t->shapes[i2];
-        PairClass c = classify(a, b, case4);
-        // SOC form: 1 every block a ball (BALL kernels), 2 every block a cone and N = 4
-        // (CONE kernels), 0 dense
-        const bool none_cone = a.soc_kind != SOC_CONE && b.soc_kind != SOC_CONE;
-        const bool all_cone = a.soc_kind != SOC_BALL && b.soc_kind != SOC_BALL;
-        if (fused_part && c.status == DCOL_OK && c.oe > 0 &&
-            fused_vid(c.N, c.nsoc, c.omax, part_lpp(c.N, c.nsoc, c.omax, c.oe, true),
-                      (none_cone && !ball_disabled()) ? LF_BALL : 0, c.oe) < 0)
-            c = classify(a, b, case4, false);
-        if (lat_part && c.status == DCOL_OK && c.oe > 0 && part_lpp(c.N, c.nsoc, c.omax, c.oe, true) < 2)
-            c = classify(a, b, case4, false);
-        // (3: box x box in the 12-row bucket -- the BOX kernels' axis-pair rows; nsoc == 0)
-        const int ball = c.nsoc == 0 ? ((a.boxp && b.boxp && c.N == 4 && c.omax == 12 && c.o == 12 && !box_disabled()) ? 3 : 0)
-                         : (none_cone && !ball_disabled()) ? 1
-                         : (all_cone && c.N == 4 && !cone_disabled()) ? 2 : 0;
-        // a row-partitioned bucket only where its SOC flavour is compiled: the x polytope
-        // (NSOC = 1) buckets exist only with ball rows, so with DCOL_NO_BALL those pairs take
-        // the dense-row kernels (N and NSOC do not depend on the partition, so `ball` stands)
-        if (c.status == DCOL_OK && c.oe > 0 && !part_flavour_built(c.N, c.nsoc, c.omax, c.oe, c.lpp, ball == 1))
-            c = classify(a, b, case4, false);
-        // flavour's own list (row-partitioned buckets have theirs: PairClass::lpp)
-        if (c.status == DCOL_OK && (ball == 1 || ball == 2) && c.oe == 0) c.lpp = choose_lpp(c.N, c.nsoc, c.omax, 2 * ball);
-        Key k = c.status == DCOL_OK ? Key{0, c.N, c.nsoc, c.omax, c.lpp, ball, 0, c.oe} : Key{1, 0, 0, 0, 0, 0, c.status, 0};
-        auto it = gid_of_key.emplace(k, (int32_t)groups.size()).first;
-        if (it->second == (int32_t)groups.size()) groups.push_back(Group{k});
-        Group& g = groups[it->second];
-        g.full = g.full && c.o == c.omax;
-        return it->second;
-    };
-    // dense cache only when it is small against the batch (its fill is O(S^2): a small
-    // batch against a big table takes the hash map)
-    const int64_t cells = (int64_t)ns * ns;
-    const bool dense = cells <= ((int64_t)1 << 22) && cells <= 16 * B + 4096;
-    std::vector<int32_t> cache(dense ? (size_t)ns * ns : 0, -1);
-    std::unordered_map<int64_t, int32_t> sparse;
-    std::vector<int32_t> gid((size_t)B);
-    for (int64_t i = 0; i < B; ++i) {
-        const int32_t i1 = s1[i], i2 = s2[i];
-        if (i1 < 0 || i1 >= ns || i2 < 0 || i2 >= ns)
-            return fail(DCOL_ERR_ARG, "shape id out of range at pair " + std::to_string(i));
-        int32_t g;
-        if (dense) {
-            int32_t& e = cache[(size_t)i1 * ns + i2];
-            if (e < 0) e = classify_pair(i1, i2);
-            g = e;
-        } else {
-            auto it = sparse.find((int64_t)i1 * ns + i2);
-            if (it == sparse.end()) it = sparse.emplace((int64_t)i1 * ns + i2, classify_pair(i1, i2)).first;
-            g = it->second;
-        }
-        gid[i] = g;
-        ++groups[g].n;
-    }
-    p->table = t;
-    p->B = B;
-    p->launches.clear();
-    perm.assign((size_t)B, 0);
-    // Latency configurations only when the whole plan cannot fill the GPU: the buckets of a
-    // large mixed plan run side by side on the fan-out streams, so each keeps its throughput
-    // configuration even when it alone would leave SIMDs idle (DCOL_LATENCY_PER_LAUNCH=1:
-    // the per-launch rule, for A/B runs).
-    static const bool per_launch = std::getenv("DCOL_LATENCY_PER_LAUNCH") != nullptr;
-    int64_t plan_lanes = 0;
-    for (const Group& G : groups)
-        if (std::get<0>(G.key) == 0) plan_lanes += G.n * std::get<4>(G.key);
-    const bool small_plan = !force_large && plan_lanes < small_lanes(t);
-    if (small_out) *small_out = small_plan;
-    int64_t at = 0;
-    for (auto& kv : gid_of_key) {   // key order
-        Group& G = groups[kv.second];
-        G.at = at;
-        Launch L;
-        L.kind = std::get<0>(G.key);
-        L.N = std::get<1>(G.key);
-        L.nsoc = std::get<2>(G.key);
-        L.omax = std::get<3>(G.key);
-        L.lpp = std::get<4>(G.key);
-        L.code = std::get<6>(G.key);
-        L.oe = std::get<7>(G.key);
-        L.full = L.kind == 0 && G.full;
-        L.ball = L.kind == 0 && std::get<5>(G.key) == 1;
-        L.cone = L.kind == 0 && std::get<5>(G.key) == 2;
-        L.box = L.kind == 0 && std::get<5>(G.key) == 3 && L.full;
-        L.slot0 = at;
-        L.n = G.n;
-        if (L.kind == 0 && !lpp_forced() && L.n * L.lpp < 64LL * t->simds && (small_plan || per_launch))
-            latency_config(L);   // cannot fill the GPU
-        at += G.n;
-        p->launches.push_back(L);
-    }
-    for (int64_t i = 0; i < B; ++i) perm[(size_t)groups[gid[i]].at++] = (int32_t)i;   // stable
-    p->small = small_plan;
-    assign_lanes(p);
-    return DCOL_SUCCESS;
-}
-
-// Mixed batches (e.g. an ALTRO phase: one victim against spheres, cylinders, capsules,
-// cones, polytopes) split into several small variant launches, each far too small to fill
-// the chip; run back to back their latencies add up.  Spread them over the caller's stream
-// plus up to kSideStreams side streams (fork/join through events) — longest-first greedy on
-// a cost estimate (waves x per-pair work), reject launches stay on the caller's stream.
-// Per-pair cost of a solve bucket in ns at full occupancy (least-squares fit to the class
-// benchmark of profiles/r03_soc/class_bench.log, within ~17 % on the 13 SOC classes): row
-// slots, SOC blocks (dense SOC rows cost more than the structured ball / cone rows) and the
-// N x N normal-matrix work; polytope x polytope buckets run at two waves per SIMD (x 0.5).
-double bucket_cost(const Launch& L) {
-    const bool dense_soc = L.nsoc > 0 && !(L.flags() & (LF_BALL | LF_CONE));
-    const double per_pair = 0.0806 * L.omax + 0.127 * L.nsoc + 0.0139 * L.N * L.N + (dense_soc ? 0.143 * L.nsoc : 0.0);
-    return (double)L.n * per_pair * (L.nsoc == 0 ? 0.5 : 1.0);
-}
-
-void assign_lanes(dcol_plan* p) {
-    int solves = 0;
-    for (const Launch& L : p->launches) solves += L.kind == 0;
-    p->lanes = 1;
-    p->issue.clear();
-    if (solves < 2) return;
-    const int lanes = std::min(solves, (p->small ? side_streams() : large_side_streams()) + 1);
-    std::vector<int> order;
-    std::vector<double> cost(p->launches.size(), 0.0);
-    for (size_t i = 0; i < p->launches.size(); ++i) {
-        const Launch& L = p->launches[i];
-        if (L.kind != 0) {
-            p->issue.push_back((int)i);   // rejects first, on the caller's stream
-            continue;
-        }
-        cost[i] = bucket_cost(L);
-        order.push_back((int)i);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-    // issued longest first: every stream starts on its biggest bucket and the short ones fill
-    // the tail, where the other streams' last kernels no longer occupy the whole chip
-    p->issue.insert(p->issue.end(), order.begin(), order.end());
-    std::vector<double> load(lanes, 0.0);
-    for (int i : order) {
-        const int l = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        p->launches[i].lane = l;
-        load[l] += cost[i];
-    }
-    static const bool serial = std::getenv("DCOL_NO_FANOUT") != nullptr;   // A/B: one stream
-    p->lanes = serial ? 1 : lanes;
-}
-
-// A plan with several solve buckets that together leave the GPU mostly idle (fewer lanes
-// than one wave per SIMD: every bucket already took its latency configuration) runs as ONE
-// fused launch; p->segs is left empty when it does not qualify (large or single-variant
-// plans, variants outside the fused kernel, DCOL_PLAN_NO_FUSE).
 // DCOL_PLAN_SUSPEND: every large solve bucket with a suspend / resume variant gets its
 // continuation buffers (entries: DCOL_SUSPEND_T per wave, default 4; DCOL_NO_SUSPEND=1
 // disables).  Allocates; returns DCOL_SUCCESS or an error.
@@ -718,7 +448,7 @@ int susp_min_env() {
 }
 int plan_susp(const dcol_table* t, dcol_plan* p) {
     const int T = susp_t_env();
-    if (T <= 0 || p->fused()) return DCOL_SUCCESS;
+    if (T <= 0 || p->lay.fused()) return DCOL_SUCCESS;   // packed plans too: ADVICE.md (kept as is)
     size_t bytes = 0;
     for (Launch& L : p->launches) {
         int f = 0;
@@ -746,162 +476,25 @@ int plan_susp(const dcol_table* t, dcol_plan* p) {
     return DCOL_SUCCESS;
 }
 
-bool plan_segments(dcol_plan* p, int (*vid_of)(int, int, int, int, int, int));
-
-// Returns 0 when fused (or not allowed), 1 when the plan does not qualify (large or
-// single-variant), 2 when it qualifies but a bucket has no case in the fused kernel.
-int plan_fuse(const dcol_table* t, dcol_plan* p, bool allow) {
-    p->segs.clear();
-    p->fused_blocks = 0;
-    p->packed = false;
-    if (!allow) return 0;
-    int solves = 0;
-    int64_t lanes = 0;
-    for (const Launch& L : p->launches)
-        if (L.kind == 0) {
-            ++solves;
-            lanes += L.n * L.lpp;
-        }
-    if (solves < 2 || solves > kMaxFusedSegs || lanes >= small_lanes(t)) return 1;
-    return plan_segments(p, fused_vid) ? 0 : 2;
-}
-
-// One segment per solve bucket with case ids from vid_of (fused_vid / packed_vid), in
-// descending per-pair cost (bucket_cost): the workgroup dispatcher hands out blocks in index
-// order as SIMDs free up, so the longest-latency waves start first and the short ones fill
-// the tail (list scheduling, longest first); DCOL_FUSED_ORDER=0: key order (A/B).  false (p
-// unchanged) when a bucket has no case.
-bool plan_segments(dcol_plan* p, int (*vid_of)(int, int, int, int, int, int)) {
-    static const bool keyorder = [] {
-        const char* e = std::getenv("DCOL_FUSED_ORDER");
-        return e && std::atoi(e) == 0;
-    }();
-    std::vector<int> order;
-    for (size_t i = 0; i < p->launches.size(); ++i)
-        if (p->launches[i].kind == 0) order.push_back((int)i);
-    if (!keyorder)
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            const Launch& A = p->launches[a];
-            const Launch& B = p->launches[b];
-            return bucket_cost(A) / (double)A.n > bucket_cost(B) / (double)B.n;
-        });
-    std::vector<FusedSeg> segs;
-    int64_t block = 0;
-    for (int i : order) {
-        const Launch& L = p->launches[i];
-        const int vid = vid_of(L.N, L.nsoc, L.omax, L.lpp, L.flags(), L.oe);
-        if (vid < 0) return false;
-        segs.push_back(FusedSeg{vid, L.lpp, block, L.slot0, L.n});
-        block += (L.n * L.lpp + kBlock - 1) / kBlock;
-    }
-    p->segs = std::move(segs);
-    p->fused_blocks = block;
-    p->packed = false;
-    p->lanes = 1;   // no fan-out
-    return true;
-}
-
-// Lanes below which a plan that is not small runs as ONE packed launch (every bucket in its
-// throughput configuration, dcol_kernels_packed.hip) instead of one launch per bucket over
-// the fan-out streams: mid-size mixed plans whose buckets each cover only part of the SIMDs
-// (a rank's shard of configs[4] at 2-8 GPUs).  16 x 64 x SIMDs (~1M lanes): measured on the
-// configs[4] shards (tools/shard_bench.py, profiles/r06_c/): packed against the fan-out
-// 0.506 / 0.549 ms at 500k pairs (775k lanes), 0.267 / 0.396 at 250k, 0.144 / 0.325 at 125k,
-// but 0.98 / 0.87 ms for the whole 1M (1.55M lanes: every bucket fills the GPU by itself and
-// its two- and three-wave kernels keep their occupancy).  DCOL_PACK_LANES=<n> for A/B runs
-// (0: never).
-int64_t pack_lanes(const dcol_table* t) {
-    static const int64_t v = [] {
-        const char* e = std::getenv("DCOL_PACK_LANES");
-        return e ? std::atoll(e) : -1LL;
-    }();
-    return v >= 0 ? v : 16LL * 64LL * t->simds;
-}
-
-// A mid-size plan (not small, below pack_lanes) with several solve buckets, every one of
-// which the packed kernel has, becomes one packed launch; otherwise p is unchanged.
-void plan_pack(const dcol_table* t, dcol_plan* p) {
-    if (p->small || p->fused()) return;
-    int solves = 0;
-    int64_t lanes = 0;
-    for (const Launch& L : p->launches)
-        if (L.kind == 0) {
-            ++solves;
-            lanes += L.n * L.lpp;
-        }
-    if (solves < 2 || solves > kMaxFusedSegs || lanes >= pack_lanes(t)) return;
-    if (!plan_segments(p, packed_vid)) return;
-    p->packed = true;
-}
-
-int bucket_and_fuse(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, dcol_plan* p,
-                    std::vector<int32_t>& perm, bool case4, bool allow_fuse) {
-    bool small = false;
-    int rc = bucket_pairs(t, B, s1, s2, p, perm, case4, false, false, &small);
-    if (rc != DCOL_SUCCESS) return rc;
-    // a plan that cannot fill the GPU: no one-lane row-partitioned buckets (bucket_pairs)
-    bool lat_part = false;
-    if (small && !lpp_forced())
-        for (const Launch& L : p->launches) lat_part = lat_part || (L.kind == 0 && L.oe > 0 && L.lpp < 2);
-    if (lat_part) {
-        rc = bucket_pairs(t, B, s1, s2, p, perm, case4, false, true);
-        if (rc != DCOL_SUCCESS) return rc;
-    }
-    // only when every bucket the fused kernel lacks is a row-partitioned one (a dense bucket
-    // without a case -- a many-row bucket -- keeps the plan unfused whatever the PART pairs
-    // do, and they would lose their faster kernels for nothing); when the re-bucketed plan
-    // still does not fuse, the first bucketing stands
-    bool only_part = true;
-    for (const Launch& L : p->launches)
-        if (L.kind == 0 && L.oe == 0 && fused_vid(L.N, L.nsoc, L.omax, L.lpp, L.flags(), 0) < 0) only_part = false;
-    if (plan_fuse(t, p, true) == 2 && only_part) {
-        rc = bucket_pairs(t, B, s1, s2, p, perm, case4, true, lat_part);
-        if (rc != DCOL_SUCCESS) return rc;
-        if (plan_fuse(t, p, true) == 2) {
-            rc = bucket_pairs(t, B, s1, s2, p, perm, case4, false, lat_part);
-            if (rc != DCOL_SUCCESS) return rc;
-        }
-    }
-    if (!allow_fuse && p->fused()) {   // same buckets, launched one by one (fan-out)
-        p->segs.clear();
-        p->fused_blocks = 0;
-        assign_lanes(p);
-    }
-    if (allow_fuse) plan_pack(t, p);   // mid-size plans: one packed launch
-    // A small plan the fused kernel cannot take (a bucket without a fused case) would fan
-    // its latency-configured buckets out over the streams, one under-filled launch after
-    // another; the packed launch of its throughput configurations serves it better (one
-    // launch, every wave placed as SIMDs free) when every bucket has a
-    // packed case.  Tried on a scratch plan: p stands unless it packs.
-    if (allow_fuse && p->small && !p->fused() && !lpp_forced() && !small_fanout()) {
-        dcol_plan q;
-        std::vector<int32_t> qperm;
-        if (bucket_pairs(t, B, s1, s2, &q, qperm, case4, false, false, nullptr, true) == DCOL_SUCCESS) {
-            q.small = false;
-            plan_pack(t, &q);
-            if (q.fused()) {
-                p->launches = std::move(q.launches);
-                p->segs = std::move(q.segs);
-                p->fused_blocks = q.fused_blocks;
-                p->packed = true;
-                p->small = false;
-                p->lanes = q.lanes;
-                p->issue.clear();
-                perm.swap(qperm);
-            }
-        }
-    }
-    return DCOL_SUCCESS;
-}
-
 int ensure_fanout(const dcol_table* tc, dcol_plan* p) {
-    if (p->lanes <= 1) return DCOL_SUCCESS;
+    if (p->lay.lanes <= 1) return DCOL_SUCCESS;
     dcol_table* t = const_cast<dcol_table*>(tc);
     DeviceGuard g(t->device);
     if (!t->side_ready) return fail(DCOL_ERR_HIP, "side streams of the device could not be created");
     hipError_t e = hipEventCreateWithFlags(&p->fork, hipEventDisableTiming);
-    for (int i = 0; e == hipSuccess && i < p->lanes - 1; ++i) e = hipEventCreateWithFlags(&p->join[i], hipEventDisableTiming);
+    for (int i = 0; e == hipSuccess && i < p->lay.lanes - 1; ++i) e = hipEventCreateWithFlags(&p->join[i], hipEventDisableTiming);
     if (e != hipSuccess) return fail(DCOL_ERR_HIP, std::string("fan-out events: ") + hipGetErrorString(e));
+    return DCOL_SUCCESS;
+}
+
+// The plan's layout under the process's policy, and its launches
+int plan_build(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, bool case4, bool allow_fuse,
+               dcol_plan* p) {
+    const int rc = plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay);
+    if (rc != DCOL_SUCCESS) return rc;
+    p->table = t;
+    p->B = B;
+    p->launches.assign(p->lay.buckets.begin(), p->lay.buckets.end());
     return DCOL_SUCCESS;
 }
 }  // namespace
@@ -921,8 +514,7 @@ int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const
     *out = nullptr;
     auto* p = new (std::nothrow) dcol_plan();
     if (!p) return fail(DCOL_ERR_NOMEM, "host allocation failed");
-    std::vector<int32_t> perm;
-    int rc = bucket_and_fuse(t, B, s1, s2, p, perm, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0);
+    int rc = plan_build(t, B, s1, s2, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0, p);
     if (rc != DCOL_SUCCESS) {
         delete p;
         return rc;
@@ -939,12 +531,13 @@ int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const
     if (e == hipSuccess) e = hipMemcpy(p->d_s2, s2, sizeof(int32_t) * B, hipMemcpyHostToDevice);
     if (e == hipSuccess && p->launches.size() > 1) {
         e = hipMalloc(&p->d_perm, sizeof(int32_t) * B);
-        if (e == hipSuccess) e = hipMemcpy(p->d_perm, perm.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->d_perm, p->lay.perm.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess && p->fused()) {
-        const size_t sb = sizeof(FusedSeg) * p->segs.size();
+    std::vector<int32_t>().swap(p->lay.perm);   // lives on the device from here on
+    if (e == hipSuccess && p->lay.fused()) {
+        const size_t sb = sizeof(FusedSeg) * p->lay.segs.size();
         e = hipMalloc(&p->d_segs, sb);
-        if (e == hipSuccess) e = hipMemcpy(p->d_segs, p->segs.data(), sb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->d_segs, p->lay.segs.data(), sb, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         dcol_plan_destroy(p);
@@ -997,20 +590,20 @@ int dcol_plan_suspended(const dcol_plan* p, int64_t* n) {
 int dcol_plan_num_launches(const dcol_plan* p, int32_t* n) {
     if (!p || !n) return fail(DCOL_ERR_ARG, "dcol_plan_num_launches: NULL argument");
     int32_t k = 0;
-    for (const Launch& L : p->launches) k += (L.kind != 0 || !p->fused());
-    *n = k + (p->fused() ? 1 : 0);
+    for (const Launch& L : p->launches) k += (L.kind != 0 || !p->lay.fused());
+    *n = k + (p->lay.fused() ? 1 : 0);
     return DCOL_SUCCESS;
 }
 
 int dcol_plan_num_streams(const dcol_plan* p, int32_t* n) {
     if (!p || !n) return fail(DCOL_ERR_ARG, "dcol_plan_num_streams: NULL argument");
-    *n = p->fused() ? 1 : p->lanes;
+    *n = p->lay.fused() ? 1 : p->lay.lanes;
     return DCOL_SUCCESS;
 }
 
 int dcol_plan_launch_form(const dcol_plan* p, int32_t* form) {
     if (!p || !form) return fail(DCOL_ERR_ARG, "dcol_plan_launch_form: NULL argument");
-    *form = !p->fused() ? DCOL_FORM_BUCKETS : (p->packed ? DCOL_FORM_PACKED : DCOL_FORM_FUSED);
+    *form = !p->lay.fused() ? DCOL_FORM_BUCKETS : (p->lay.packed ? DCOL_FORM_PACKED : DCOL_FORM_FUSED);
     return DCOL_SUCCESS;
 }
 
@@ -1056,7 +649,7 @@ bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t*
         const char* e = std::getenv("DCOL_NO_ORDER_HINT");
         return e && *e && *e != '0';
     }();
-    if (off || p->fused() || p->B >= (int64_t)1 << 31) return false;
+    if (off || p->lay.fused() || p->B >= (int64_t)1 << 31) return false;
     bool any = false;
     for (const Launch& L : p->launches) any = any || (L.kind == 0 && !L.susp);
     if (!any) return false;
@@ -1099,7 +692,7 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     // launched on the null stream: the server runs on a blocking stream (CU-masked streams
     // have no non-blocking form), so null-stream work waits for it to leave, i.e. for its idle
     // time (DCOL_PAIR_SERVER_IDLE_US) -- asking it to leave now costs a restart instead.
-    if (yield && (!p->small || stream == nullptr)) yield_pair_servers(p->table->device);
+    if (yield && (!p->lay.small || stream == nullptr)) yield_pair_servers(p->table->device);
     if (p->B == 0) return DCOL_SUCCESS;
     if (!pose1 || !pose2 || (!alpha && !rec))
         return fail(DCOL_ERR_ARG, "dcol_plan_run: pose1, pose2 and alpha are required");
@@ -1138,7 +731,7 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     a.susp_cap = 0;
     // a run without envelope / implicit gradients may take a bucket's FD-only copy (LF_FDONLY)
     const int fdonly = (flags & (DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)) ? 0 : LF_FDONLY;
-    const bool fan = p->lanes > 1 && p->fork;
+    const bool fan = p->lay.lanes > 1 && p->fork;
     hipError_t e = hipSuccess;
     // (before the fork: the side streams' launches then follow a new state's zero fill)
     const uint8_t* hint_r = nullptr;
@@ -1146,13 +739,13 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     const bool hinted = hint && plan_hints(p, st, &hint_r, &hint_w);
     if (fan) {
         e = hipEventRecord(p->fork, st);
-        for (int l = 1; e == hipSuccess && l < p->lanes; ++l) e = hipStreamWaitEvent(t->side[l - 1], p->fork, 0);
+        for (int l = 1; e == hipSuccess && l < p->lay.lanes; ++l) e = hipStreamWaitEvent(t->side[l - 1], p->fork, 0);
         if (e != hipSuccess) return fail(DCOL_ERR_HIP, std::string("dcol_plan_run fork: ") + hipGetErrorString(e));
     }
     const size_t nl = p->launches.size();
     for (size_t li = 0; li < nl; ++li) {
-        const Launch& L = p->launches[p->issue.size() == nl ? (size_t)p->issue[li] : li];
-        if (L.kind == 0 && p->fused()) continue;   // covered by the fused launch below
+        const Launch& L = p->launches[p->lay.issue.size() == nl ? (size_t)p->lay.issue[li] : li];
+        if (L.kind == 0 && p->lay.fused()) continue;   // covered by the fused launch below
         a.slot0 = L.slot0;
         a.n = L.n;
         hipStream_t ls = (fan && L.lane > 0) ? t->side[L.lane - 1] : st;
@@ -1184,14 +777,14 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
         }
         if (e != hipSuccess) break;
     }
-    if (e == hipSuccess && p->fused()) {
+    if (e == hipSuccess && p->lay.fused()) {
         a.slot0 = 0;
         a.n = 0;
-        e = p->packed ? launch_packed(a, p->d_segs, (int)p->segs.size(), p->fused_blocks, st)
-                      : launch_fused(a, p->d_segs, (int)p->segs.size(), p->fused_blocks, st);
+        e = p->lay.packed ? launch_packed(a, p->d_segs, (int)p->lay.segs.size(), p->lay.fused_blocks, st)
+                          : launch_fused(a, p->d_segs, (int)p->lay.segs.size(), p->lay.fused_blocks, st);
     }
     if (fan) {   // join even after a failed launch, so the side streams never run ahead
-        for (int l = 1; l < p->lanes; ++l) {
+        for (int l = 1; l < p->lay.lanes; ++l) {
             hipError_t j = hipEventRecord(p->join[l - 1], t->side[l - 1]);
             if (j == hipSuccess) j = hipStreamWaitEvent(st, p->join[l - 1], 0);
             if (e == hipSuccess) e = j;
@@ -1308,8 +901,8 @@ int dcol_prox_pair(const dcol_table* tc, int32_t s1, int32_t s2, const double* p
     std::memcpy(h->pose1, pose1, 6 * sizeof(double));
     std::memcpy(h->pose2, pose2, 6 * sizeof(double));
     // SoA of one pair = the 6 values in order; the kernel reads / writes the mapped memory.
-    const bool single = plan->launches.size() == 1 && plan->launches[0].kind == 0 && !plan->fused() &&
-                         !plan->launches[0].susp && plan->lanes <= 1;
+    const bool single = plan->launches.size() == 1 && plan->launches[0].kind == 0 && !plan->lay.fused() &&
+                         !plan->launches[0].susp && plan->lay.lanes <= 1;
     // The one-pair server (PairBox, dcol_kernels_server.hip): a resident workgroup polls the
     // mailbox, so a call whose variant the fused kernel has (the server switches over the
     // same solver copies) costs no launch.
@@ -1576,8 +1169,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     dcol_table* t = const_cast<dcol_table*>(tc);
     std::lock_guard<std::mutex> lk(t->mu);
     dcol_plan p;   // transient, device arrays are views into the table's staging buffer
-    std::vector<int32_t> perm;
-    int rc = bucket_and_fuse(t, B, s1, s2, &p, perm, (flags & DCOL_CASE4) != 0, true);
+    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p);
     if (rc != DCOL_SUCCESS) return rc;
     rc = ensure_fanout(t, &p);
     if (rc != DCOL_SUCCESS) return rc;
@@ -1585,7 +1177,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     // staging: doubles pose1[6B] pose2[6B] | alpha[B] contact[3B] grad[12B] ; fused segments ;
     // ints s1 s2 perm iters status
     const size_t nin = (size_t)12 * B, nout = (size_t)16 * B;
-    const size_t segb = sizeof(FusedSeg) * p.segs.size();
+    const size_t segb = sizeof(FusedSeg) * p.lay.segs.size();
     const size_t bytes = (nin + nout) * sizeof(double) + segb + 5 * (size_t)B * sizeof(int32_t);
     if (t->stage_bytes < bytes) {
         if (t->stage) (void)hipFree(t->stage);
@@ -1601,7 +1193,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     double* dct = dal + B;
     double* dgr = dct + 3 * B;
     FusedSeg* dsg = reinterpret_cast<FusedSeg*>(dp1 + nin + nout);
-    p.d_segs = p.fused() ? dsg : nullptr;
+    p.d_segs = p.lay.fused() ? dsg : nullptr;
     int32_t* ib = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(dsg) + segb);
     p.d_s1 = ib;
     p.d_s2 = ib + B;
@@ -1629,11 +1221,11 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
         }
     std::memcpy(ids, s1, sizeof(int32_t) * B);
     std::memcpy(ids + B, s2, sizeof(int32_t) * B);
-    std::memcpy(ids + 2 * B, perm.data(), sizeof(int32_t) * B);
+    std::memcpy(ids + 2 * B, p.lay.perm.data(), sizeof(int32_t) * B);
     // one H2D copy: [pose1 soa | pose2 soa] then [s1 | s2 | perm]
     hipError_t e = hipMemcpy(dp1, soa, sizeof(double) * nin, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ib, ids, sizeof(int32_t) * 3 * B, hipMemcpyHostToDevice);
-    if (e == hipSuccess && segb) e = hipMemcpy(dsg, p.segs.data(), segb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && segb) e = hipMemcpy(dsg, p.lay.segs.data(), segb, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(DCOL_ERR_HIP, std::string("dcol_prox_batch_host H2D: ") + hipGetErrorString(e));
     rc = plan_run_rec(&p, dp1, dp2, tol, max_iter, flags, dal, dct, dgr, dit, dst, nullptr, nullptr, true, false);
     if (rc != DCOL_SUCCESS) return rc;

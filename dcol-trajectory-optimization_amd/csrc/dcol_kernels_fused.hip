@@ -11,16 +11,7 @@
 // a wave never mixes variants and never diverges on structure.
 #include "dcol_device.hpp"
 #include "dcol_launch.hpp"
-#include "dcol_variants.inc"
-
-// Development builds (make dev): no cases -- plans launch per bucket (fan-out), and this
-// unit, whose compile time is the sum of its ~100 solver copies, builds in seconds.
-#ifdef DCOL_NO_FUSED_CASES
-#undef DCOL_FUSED_VARIANTS
-#define DCOL_FUSED_VARIANTS(X)
-#undef DCOL_FUSED_PART_VARIANTS
-#define DCOL_FUSED_PART_VARIANTS(X)
-#endif
+#include "dcol_cases.hpp"   // (development builds, make dev: no cases)
 
 namespace dcol {
 
@@ -50,30 +41,6 @@ __global__ void __launch_bounds__(kSolveBlock, 1) prox_fused_kernel(KArgs A, con
         default:
             break;
     }
-}
-
-// (a bucket whose pairs all fill OMAX takes the padding-free case if there is one, a bucket
-// of ball-SOC or cone-SOC pairs the structured case, else the plain one -- as the
-// per-variant launchers do)
-int fused_vid(int N, int nsoc, int omax, int lpp, int flags, int oe) {
-    if (oe > 0) {   // row-partitioned bucket: FULL|BALL, BALL, FULL, dense
-        for (const int want : {(int)(LF_FULL | LF_BALL), (int)LF_BALL, (int)LF_FULL, 0}) {
-            if ((want & flags) != want) continue;
-#define DCOL_FPID(ID, NN, NS, OM, LP, FL, OEE) \
-    if (NN == N && NS == nsoc && OM == omax && OEE == oe && LP == lpp && FL == want) return ID;
-            DCOL_FUSED_PART_VARIANTS(DCOL_FPID)
-#undef DCOL_FPID
-        }
-        return -1;
-    }
-    for (const int want : {(int)LF_FULL, (int)LF_BALL, (int)LF_CONE, 0}) {
-        if ((want & flags) != want) continue;
-#define DCOL_FID(ID, NN, NS, OM, LP, FL) \
-    if (NN == N && NS == nsoc && OM == omax && LP == lpp && FL == want) return ID;
-        DCOL_FUSED_VARIANTS(DCOL_FID)
-#undef DCOL_FID
-    }
-    return -1;
 }
 
 hipError_t launch_fused(const KArgs& args, const FusedSeg* d_segs, int nseg, int64_t blocks, hipStream_t stream) {

@@ -7,7 +7,7 @@
 // one -- even three streams at a time -- the step is a chain of under-filled launches
 // (0.32 ms per 125k pairs, where 1M pairs take 0.85 ms).  Here one launch carries all of
 // them: workgroup w finds its segment (bucket) in the segment table, segments in descending
-// per-pair cost (dcol_capi.cpp plan_pack), and switches to that bucket's solver copy.  The
+// per-pair cost (dcol_plan.hpp plan_pack), and switches to that bucket's solver copy.  The
 // kernel runs one wave per SIMD (its register allocation is the maximum over the cases), so
 // the hardware dispatcher places each next workgroup on the next SIMD that frees up: list
 // scheduling of every bucket's waves, longest first, instead of stream chains.
@@ -18,12 +18,7 @@
 // results are bitwise those of the per-bucket launches.
 #include "dcol_device.hpp"
 #include "dcol_launch.hpp"
-#include "dcol_variants.inc"
-
-#ifdef DCOL_NO_PACKED_CASES   // development builds (make dev): plans launch per bucket
-#undef DCOL_PACKED_VARIANTS
-#define DCOL_PACKED_VARIANTS(X)
-#endif
+#include "dcol_cases.hpp"   // (development builds, make dev: no cases, plans launch per bucket)
 
 namespace dcol {
 
@@ -48,17 +43,6 @@ __global__ void __launch_bounds__(kSolveBlock, 1) prox_packed_kernel(KArgs A, co
         default:
             break;
     }
-}
-
-// the case of a bucket: the first entry of its shape (and LPP) whose flavour the bucket's
-// launch flags allow -- the list is in the per-variant launchers' preference order
-int packed_vid(int N, int nsoc, int omax, int lpp, int flags, int oe) {
-#define DCOL_KID(ID, NN, NS, OM, LP, FL, OEE) \
-    if (NN == N && NS == nsoc && OM == omax && LP == lpp && OEE == oe && (FL & flags) == FL) return ID;
-    DCOL_PACKED_VARIANTS(DCOL_KID)
-#undef DCOL_KID
-    (void)N; (void)nsoc; (void)omax; (void)lpp; (void)flags; (void)oe;
-    return -1;
 }
 
 hipError_t launch_packed(const KArgs& args, const FusedSeg* d_segs, int nseg, int64_t blocks, hipStream_t stream) {

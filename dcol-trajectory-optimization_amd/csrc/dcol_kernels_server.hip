@@ -13,14 +13,7 @@
 // grid always drains.
 #include "dcol_device.hpp"
 #include "dcol_launch.hpp"
-#include "dcol_variants.inc"
-
-#ifdef DCOL_NO_FUSED_CASES   // development builds: no cases (dcol_prox_pair then launches per call)
-#undef DCOL_FUSED_VARIANTS
-#define DCOL_FUSED_VARIANTS(X)
-#undef DCOL_FUSED_PART_VARIANTS
-#define DCOL_FUSED_PART_VARIANTS(X)
-#endif
+#include "dcol_cases.hpp"   // (development builds: no cases, dcol_prox_pair then launches per call)
 
 namespace dcol {
 

@@ -9,7 +9,7 @@ enum : int { LF_FULL = 1, LF_BALL = 2, LF_CONE = 4, LF_BOX = 8, LF_SPLIT = 32, L
 // (LF_FDONLY: a run without envelope / implicit gradients; LF_SPLIT: DCOL_SPLIT=1 opt-in)
 constexpr int kBlock = kSolveBlock;   // threads per workgroup of the solve kernel
 constexpr int kSideStreams = 7;   // capacity of the extra streams for concurrent variant launches
-                                  // (dcol_capi.cpp side_streams(): 3 by default, DCOL_SIDE_STREAMS)
+                                  // (dcol_plan.hpp PlanPolicy::side_streams: 3 by default, DCOL_SIDE_STREAMS)
 // Grid of a prox_kernel launch: n * lpp threads mapped linearly, or -- with an order hint
 // (KArgs hint_wins > 0, dcol_device.hpp hint_wave_slot) -- hint_ww waves for each of the
 // hint_wins windows, phantom ones included (they exit at once)
@@ -48,13 +48,11 @@ constexpr int kMaxFusedSegs = 64;
 // suspend / resume launch pairs (dcol_kernels_susp.hip)
 bool susp_available(int N, int nsoc, int omax, int lpp, int flags, int oe, int* fields);
 hipError_t launch_susp(int N, int nsoc, int omax, int lpp, int flags, int oe, const KArgs& args, hipStream_t stream);
-// fused variant id of a kernel shape + (lpp, launch flags, PART extra slots oe), or -1 if
-// the fused kernel lacks it
-int fused_vid(int N, int nsoc, int omax, int lpp, int flags, int oe = 0);
+// fused launch (dcol_kernels_fused.hip; segments' vid from dcol_plan.hpp fused_vid)
 hipError_t launch_fused(const KArgs& args, const FusedSeg* d_segs, int nseg, int64_t blocks, hipStream_t stream);
 // packed multi-bucket launch (dcol_kernels_packed.hip): a mid-size plan's buckets in their
-// throughput configurations in ONE launch (segments as FusedSeg, vid = packed case id)
-int packed_vid(int N, int nsoc, int omax, int lpp, int flags, int oe = 0);
+// throughput configurations in ONE launch (segments as FusedSeg, vid = packed case id:
+// dcol_plan.hpp packed_vid)
 hipError_t launch_packed(const KArgs& args, const FusedSeg* d_segs, int nseg, int64_t blocks, hipStream_t stream);
 
 // Mailbox of the one-pair server (dcol_prox_pair; dcol_kernels_server.hip prox_pair_server):

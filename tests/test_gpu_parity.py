@@ -105,7 +105,7 @@ def test_fused_launch_matches_per_bucket_launches(engine, name):
 
 def test_large_shape_table_sparse_bucketing():
     """A table of more than 2,048 shapes takes the hashed (shape1, shape2) class cache of
-    dcol_capi.cpp: bucket_pairs instead of the dense S x S one; the plan (buckets, slot
+    dcol_plan.hpp: bucket_pairs instead of the dense S x S one; the plan (buckets, slot
     order, variants) and therefore the results must be bitwise those of a small table."""
     from dcol_amd import Engine, ShapeSpec, spec_from_arrays
     d = load_golden([p for p in golden_files() if p.endswith("synthetic_mixed.npz")][0])

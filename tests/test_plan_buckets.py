@@ -1,7 +1,8 @@
 """Plan bucketing through the C-ABI (dcol_plan_bucket): which kernel variant and lane
-configuration a plan launches -- the host logic of dcol_capi.cpp bucket_pairs /
-bucket_and_fuse.  Plans need a table on the device, so these run on the GPU box; no solve is
-launched."""
+configuration a plan launches -- the plan policy of csrc/dcol_plan.hpp (plan_layout) as
+dcol_capi.cpp applies it.  Plans need a table on the device, so these run on the GPU box
+(the policy alone runs on the CPU: tests/test_plan_layout.py); no solve is launched, the
+bitwise comparison of the packed launch aside."""
 import numpy as np
 import pytest
 
@@ -77,6 +78,34 @@ def test_small_polygon_box_plan_skips_one_lane_buckets(engine, B):
     b = _solves(_polygon_box(engine, B))
     assert b and all(not (x["oe"] > 0 and x["lpp"] < 2) for x in b)
     assert all(x["oe"] == 0 and x["lpp"] >= 4 for x in b)
+
+
+def test_recorded_layouts_through_the_c_abi(engine):
+    """tests/plan_layouts.json (tools/record_plan_layouts.py: what the library's plans launched
+    when the policy was recorded) through the real C-ABI, default environment: every plan's
+    ordered buckets, launches, streams and launch form.  No kernel runs."""
+    import json
+    import os
+    import torch
+    import plan_cases
+    if any(os.environ.get(k) for k in plan_cases.POLICY_VARS):
+        pytest.skip("plan policy overridden by the environment")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "plan_layouts.json")) as f:
+        rec = json.load(f)
+    simds = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    if simds != rec["simds"]:
+        pytest.skip(f"the record is of a device with {rec['simds']} SIMDs, this one has {simds}")
+    ids = {name: _ids(engine, plan_cases.table(name)) for name in plan_cases.TABLES}
+    for p in rec["plans"]:
+        if p["env"]:
+            continue
+        s1, s2 = plan_cases.pairs(p["table"], p["B"], rec["pair_seed"])
+        emap = ids[p["table"]]
+        plan = engine.plan(emap[s1], emap[s2], cache=False, case4=bool(p["options"] & 1), fuse=not (p["options"] & 2))
+        where = (p["table"], p["B"], p["options"])
+        assert [plan_cases.bucket_row(b) for b in plan.buckets()] == p["buckets"], where
+        assert (plan.num_launches, plan.num_streams, plan.launch_form) == (
+            p["num_launches"], p["num_streams"], p["launch_form"]), where
 
 
 def test_bucket_index_checked(engine):
