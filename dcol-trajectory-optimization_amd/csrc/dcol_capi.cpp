@@ -139,6 +139,8 @@ __global__ void __launch_bounds__(256) reject_kernel(KArgs A, int32_t code) {
         for (int q = 0; q < 3; ++q) A.contact[q * B + pi] = nan;
     if ((A.flags & (F_GRAD_FD | F_GRAD_ENV | F_GRAD_IMP)) && A.grad)
         for (int q = 0; q < 12; ++q) A.grad[q * B + pi] = nan;
+    if ((A.flags & F_JAC) && A.jac)
+        for (int q = 0; q < 48; ++q) A.jac[q * B + pi] = nan;
     if (A.rec) {
         double* r = A.rec + (int64_t)kRec * pi;
         for (int q = 0; q < 13; ++q) r[q] = nan;
@@ -209,6 +211,7 @@ struct dcol_plan {
     hipEvent_t join[kSideStreams] = {};
     FusedSeg* d_segs = nullptr;  // lay.segs on the device
     void* d_susp = nullptr;      // DCOL_PLAN_SUSPEND scratch (one allocation for every such launch)
+    bool jac = false;            // DCOL_PLAN_JACOBIAN: dense-row buckets (plan_layout_jac), no order hint
     // Order-hint state (plan_hints; dcol_device.hpp hint_wave_slot): per stream the plan has
     // run on, two zero-filled uint8[B] buffers (one allocation), indexed by global slot.  Run k
     // on the stream reads buf[k % 2] and writes buf[(k + 1) % 2]: within one launch a window's
@@ -300,6 +303,16 @@ hipError_t launch_variant(int N, int nsoc, int omax, int lpp, int flags, const K
     if (N == 6) return launch_n6(nsoc, omax, lpp, flags, a, st);
     if (N == 7) return launch_n7(nsoc, omax, lpp, flags, a, st);
     if (N == 8) return launch_n8(nsoc, omax, lpp, flags, a, st);
+    return hipErrorInvalidValue;
+}
+
+// the contact-point Jacobian copy of a dense-row bucket (dcol_kernels_jac.hip)
+hipError_t launch_jac(int N, int nsoc, int omax, int lpp, const KArgs& a, hipStream_t st) {
+    if (N == 4) return launch_jac_n4(nsoc, omax, lpp, a, st);
+    if (N == 5) return launch_jac_n5(nsoc, omax, lpp, a, st);
+    if (N == 6) return launch_jac_n6(nsoc, omax, lpp, a, st);
+    if (N == 7) return launch_jac_n7(nsoc, omax, lpp, a, st);
+    if (N == 8) return launch_jac_n8(nsoc, omax, lpp, a, st);
     return hipErrorInvalidValue;
 }
 
@@ -489,9 +502,11 @@ int ensure_fanout(const dcol_table* tc, dcol_plan* p) {
 
 // The plan's layout under the process's policy, and its launches
 int plan_build(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, bool case4, bool allow_fuse,
-               dcol_plan* p) {
-    const int rc = plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay);
+               dcol_plan* p, bool jac = false) {
+    const int rc = jac ? plan_layout_jac(t->shapes, t->simds, B, s1, s2, case4, plan_policy(), p->lay)
+                       : plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay);
     if (rc != DCOL_SUCCESS) return rc;
+    p->jac = jac;
     p->table = t;
     p->B = B;
     p->launches.assign(p->lay.buckets.begin(), p->lay.buckets.end());
@@ -508,13 +523,16 @@ int dcol_plan_create(const dcol_table* t, int64_t B, const int32_t* s1, const in
 int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, int32_t options,
                         dcol_plan** out) {
     if (!t || !out || B < 0 || (B > 0 && (!s1 || !s2))) return fail(DCOL_ERR_ARG, "dcol_plan_create: bad arguments");
-    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND))
+    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND | DCOL_PLAN_JACOBIAN))
         return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: unknown option bits");
+    if ((options & DCOL_PLAN_JACOBIAN) && (options & DCOL_PLAN_SUSPEND))
+        return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: DCOL_PLAN_JACOBIAN cannot be combined with DCOL_PLAN_SUSPEND");
     if (B > INT32_MAX) return fail(DCOL_ERR_ARG, "dcol_plan_create: B exceeds 2^31-1");
     *out = nullptr;
     auto* p = new (std::nothrow) dcol_plan();
     if (!p) return fail(DCOL_ERR_NOMEM, "host allocation failed");
-    int rc = plan_build(t, B, s1, s2, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0, p);
+    int rc = plan_build(t, B, s1, s2, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0, p,
+                        (options & DCOL_PLAN_JACOBIAN) != 0);
     if (rc != DCOL_SUCCESS) {
         delete p;
         return rc;
@@ -649,7 +667,7 @@ bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t*
         const char* e = std::getenv("DCOL_NO_ORDER_HINT");
         return e && *e && *e != '0';
     }();
-    if (off || p->lay.fused() || p->B >= (int64_t)1 << 31) return false;
+    if (off || p->jac || p->lay.fused() || p->B >= (int64_t)1 << 31) return false;
     bool any = false;
     for (const Launch& L : p->launches) any = any || (L.kind == 0 && !L.susp);
     if (!any) return false;
@@ -686,13 +704,19 @@ bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t*
 // runs once, nor dcol_prox_pair's one-pair plans, which have nothing to order)
 int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, double tol, int32_t max_iter,
                  int32_t flags, double* alpha, double* contact, double* grad, int32_t* iters, int32_t* status,
-                 double* rec, void* stream, bool yield = true, bool hint = true) {
+                 double* rec, void* stream, bool yield = true, bool hint = true, double* jac = nullptr) {
     if (!p) return fail(DCOL_ERR_ARG, "dcol_plan_run: NULL plan");
     // (the pair call's own launch path keeps it).  A small plan keeps it too -- unless it is
     // launched on the null stream: the server runs on a blocking stream (CU-masked streams
     // have no non-blocking form), so null-stream work waits for it to leave, i.e. for its idle
     // time (DCOL_PAIR_SERVER_IDLE_US) -- asking it to leave now costs a restart instead.
     if (yield && (!p->lay.small || stream == nullptr)) yield_pair_servers(p->table->device);
+    // The contact-point Jacobian: jac is set by dcol_plan_run_jac alone, after its checks, and
+    // then the plan's dense-row buckets launch their Jacobian copies.  The kernels' F_JAC bit
+    // follows jac, so DCOL_JACOBIAN in any other caller's flags is dropped here (it had no
+    // meaning before ABI 5).
+    const bool want_jac = jac != nullptr;
+    flags = want_jac ? (flags | DCOL_JACOBIAN) : (flags & ~DCOL_JACOBIAN);
     if (p->B == 0) return DCOL_SUCCESS;
     if (!pose1 || !pose2 || (!alpha && !rec))
         return fail(DCOL_ERR_ARG, "dcol_plan_run: pose1, pose2 and alpha are required");
@@ -729,6 +753,7 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     a.susp_pi = nullptr;
     a.susp_state = nullptr;
     a.susp_cap = 0;
+    a.jac = want_jac ? jac : nullptr;
     // a run without envelope / implicit gradients may take a bucket's FD-only copy (LF_FDONLY)
     const int fdonly = (flags & (DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)) ? 0 : LF_FDONLY;
     const bool fan = p->lay.lanes > 1 && p->fork;
@@ -763,6 +788,8 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
             b.susp_cap = L.susp_cap;
             e = hipMemsetAsync(L.d_susp_count, 0, sizeof(int32_t), ls);
             if (e == hipSuccess) e = launch_susp(L.N, L.nsoc, L.omax, L.lpp, L.flags(), L.oe, b, ls);
+        } else if (want_jac) {   // (a Jacobian plan: dense rows, no hint)
+            e = launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls);
         } else {
             const int split = (L.oe > 0 && L.lpp == 2 && split_enabled() && split_built(L.N, L.nsoc, L.omax, L.oe))
                                   ? LF_SPLIT : 0;
@@ -801,6 +828,18 @@ int dcol_plan_run(const dcol_plan* p, const double* pose1, const double* pose2, 
                   int32_t flags, double* alpha, double* contact, double* grad, int32_t* iters, int32_t* status,
                   void* stream) {
     return plan_run_rec(p, pose1, pose2, tol, max_iter, flags, alpha, contact, grad, iters, status, nullptr, stream);
+}
+
+int dcol_plan_run_jac(const dcol_plan* p, const double* pose1, const double* pose2, double tol, int32_t max_iter,
+                      int32_t flags, double* alpha, double* contact, double* grad, double* jac, int32_t* iters,
+                      int32_t* status, void* stream) {
+    if (!p) return fail(DCOL_ERR_ARG, "dcol_plan_run_jac: NULL plan");
+    const bool want = (flags & DCOL_JACOBIAN) != 0;
+    if (want && !p->jac)
+        return fail(DCOL_ERR_ARG, "dcol_plan_run_jac: DCOL_JACOBIAN needs a plan made with DCOL_PLAN_JACOBIAN");
+    if (want && !jac) return fail(DCOL_ERR_ARG, "dcol_plan_run_jac: DCOL_JACOBIAN needs jac[]");
+    return plan_run_rec(p, pose1, pose2, tol, max_iter, flags, alpha, contact, grad, iters, status, nullptr, stream,
+                        true, true, want ? jac : nullptr);
 }
 
 int dcol_prox_pair(const dcol_table* tc, int32_t s1, int32_t s2, const double* pose1, const double* pose2, double tol,
@@ -1159,9 +1198,11 @@ int dcol_debug_exec_selftest(uint64_t* counted) {
 }
 #endif
 
-int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, const int32_t* s2, const double* pose1,
-                         const double* pose2, double tol, int32_t max_iter, int32_t flags, double* alpha,
-                         double* contact, double* grad, int32_t* iters, int32_t* status) {
+// dcol_prox_batch_host, and with jac (host [B][4][12]) dcol_prox_jacobian_host: the same
+// staging with 48 B more output doubles behind the gradient, a DCOL_PLAN_JACOBIAN layout
+static int prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, const int32_t* s2, const double* pose1,
+                           const double* pose2, double tol, int32_t max_iter, int32_t flags, double* alpha,
+                           double* contact, double* grad, double* jac, int32_t* iters, int32_t* status) {
     if (!tc || B < 0) return fail(DCOL_ERR_ARG, "dcol_prox_batch_host: bad arguments");
     if (B == 0) return DCOL_SUCCESS;
     if (!s1 || !s2 || !pose1 || !pose2 || !alpha) return fail(DCOL_ERR_ARG, "dcol_prox_batch_host: NULL array");
@@ -1169,14 +1210,14 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     dcol_table* t = const_cast<dcol_table*>(tc);
     std::lock_guard<std::mutex> lk(t->mu);
     dcol_plan p;   // transient, device arrays are views into the table's staging buffer
-    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p);
+    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p, jac != nullptr);
     if (rc != DCOL_SUCCESS) return rc;
     rc = ensure_fanout(t, &p);
     if (rc != DCOL_SUCCESS) return rc;
     DeviceGuard g(t->device);
     // staging: doubles pose1[6B] pose2[6B] | alpha[B] contact[3B] grad[12B] ; fused segments ;
     // ints s1 s2 perm iters status
-    const size_t nin = (size_t)12 * B, nout = (size_t)16 * B;
+    const size_t nin = (size_t)12 * B, nout = (size_t)(jac ? 64 : 16) * B;
     const size_t segb = sizeof(FusedSeg) * p.lay.segs.size();
     const size_t bytes = (nin + nout) * sizeof(double) + segb + 5 * (size_t)B * sizeof(int32_t);
     if (t->stage_bytes < bytes) {
@@ -1192,6 +1233,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     double* dal = dp1 + nin;
     double* dct = dal + B;
     double* dgr = dct + 3 * B;
+    double* djc = jac ? dgr + 12 * B : nullptr;
     FusedSeg* dsg = reinterpret_cast<FusedSeg*>(dp1 + nin + nout);
     p.d_segs = p.lay.fused() ? dsg : nullptr;
     int32_t* ib = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(dsg) + segb);
@@ -1227,7 +1269,7 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     if (e == hipSuccess) e = hipMemcpy(ib, ids, sizeof(int32_t) * 3 * B, hipMemcpyHostToDevice);
     if (e == hipSuccess && segb) e = hipMemcpy(dsg, p.lay.segs.data(), segb, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(DCOL_ERR_HIP, std::string("dcol_prox_batch_host H2D: ") + hipGetErrorString(e));
-    rc = plan_run_rec(&p, dp1, dp2, tol, max_iter, flags, dal, dct, dgr, dit, dst, nullptr, nullptr, true, false);
+    rc = plan_run_rec(&p, dp1, dp2, tol, max_iter, flags, dal, dct, dgr, dit, dst, nullptr, nullptr, true, false, djc);
     if (rc != DCOL_SUCCESS) return rc;
     e = hipMemcpy(outd, dal, sizeof(double) * nout, hipMemcpyDeviceToHost);   // synchronises
     if (e == hipSuccess) e = hipMemcpy(ids + 3 * B, dit, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost);
@@ -1241,7 +1283,26 @@ int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, con
     if (grad && (flags & DCOL_GRAD_ANY))
         for (int64_t i = 0; i < B; ++i)
             for (int q = 0; q < 12; ++q) grad[12 * i + q] = outd[(size_t)4 * B + q * B + i];
+    if (jac)
+        for (int64_t i = 0; i < B; ++i)
+            for (int q = 0; q < 48; ++q) jac[48 * i + q] = outd[(size_t)16 * B + q * B + i];
     return DCOL_SUCCESS;
+}
+
+int dcol_prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, const int32_t* s2, const double* pose1,
+                         const double* pose2, double tol, int32_t max_iter, int32_t flags, double* alpha,
+                         double* contact, double* grad, int32_t* iters, int32_t* status) {
+    return prox_batch_host(tc, B, s1, s2, pose1, pose2, tol, max_iter, flags, alpha, contact, grad, nullptr, iters,
+                           status);
+}
+
+int dcol_prox_jacobian_host(const dcol_table* tc, int64_t B, const int32_t* s1, const int32_t* s2, const double* pose1,
+                            const double* pose2, double tol, int32_t max_iter, int32_t flags, double* alpha,
+                            double* contact, double* grad, double* jac, int32_t* iters, int32_t* status) {
+    if (!jac && B > 0) return fail(DCOL_ERR_ARG, "dcol_prox_jacobian_host: jac is required");
+    if ((flags & DCOL_CONTACT) && !contact) return fail(DCOL_ERR_ARG, "dcol_prox_jacobian_host: DCOL_CONTACT needs contact");
+    if ((flags & DCOL_GRAD_ANY) && !grad) return fail(DCOL_ERR_ARG, "dcol_prox_jacobian_host: gradient flag needs grad");
+    return prox_batch_host(tc, B, s1, s2, pose1, pose2, tol, max_iter, flags, alpha, contact, grad, jac, iters, status);
 }
 
 }  // extern "C"

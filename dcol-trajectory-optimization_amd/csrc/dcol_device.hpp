@@ -97,7 +97,7 @@ DCOL_HD bool pos_finite(double x) {
 enum : int32_t { ST_OK = 0, ST_MAXITER = 1, ST_UNSUPPORTED = 2, ST_NOT_PD = 3, ST_NONFINITE = 4, ST_TOO_LARGE = 5 };
 constexpr int32_t ST_SUSPENDED = 100;   // internal: handed to the resume launch (never reported)
 enum : int32_t { SOC_NONE = 0, SOC_BALL = 1, SOC_CONE = 2 };
-enum : int32_t { F_GRAD_FD = 1, F_GRAD_ENV = 2, F_CONTACT = 4, F_GRAD_IMP = 16 };
+enum : int32_t { F_GRAD_FD = 1, F_GRAD_ENV = 2, F_CONTACT = 4, F_GRAD_IMP = 16, F_JAC = 64 };
 
 // One primitive, pre-digested on the host (dcol_capi.cpp: digest_shape()).
 struct DevShape {
@@ -192,6 +192,10 @@ struct KArgs {
     uint8_t* __restrict__ hint_w = nullptr;
     int32_t hint_wins = 0;
     int32_t hint_ww = 0;
+    // [4][12][B] contact-point Jacobian d[x0, x1, x2, alpha] / d[r1, p1, r2, p2], component
+    // (k, j) at (12 k + j) B + pi; written by the JAC copies (solve_one JAC) of a run with
+    // F_JAC, nullptr: none
+    double* __restrict__ jac = nullptr;
 #ifdef DCOL_STAMPS
     unsigned long long* stamps = nullptr;   // diagnostic build only (tools/stamp_probe.hip, the pair
                                             // server of lib_stamps): [B][16]; nullptr: none
@@ -2370,6 +2374,145 @@ struct Solver {
             g[3 + j] -= acc;
         }
     }
+
+    // -------- contact-point Jacobian (DCOL_JACOBIAN; the JAC copies) --------------------
+    // d[x0, x1, x2, alpha] / d theta at the returned iterate (DESIGN.md "gradient modes").
+    // The KKT conditions G'z + c = 0, G x + s = h, s o z = const differentiated in a pose
+    // coordinate with the residuals held fixed:
+    //   G'dz = -dG'z,  G dx + ds = dh - dG x,  L(z) ds + L(s) dz = 0,
+    // L(v) = diag(v) on orthant rows, the arrow matrix of v on a SOC block (L(u) w = u o w).
+    // With D = L(s)^-1 L(z), i.e. D u = s \ (z o u) (z / s on orthant rows; a dense 4 x 4 block
+    // per SOC block, NOT symmetric off the central path):
+    //   H dx = -dG'z - G'D (dG x - dh),  H = G'D G   (N x N, non-symmetric).
+    // Adjoint form, one output row k at a time: v_k = H^-T e_k, a_k = -D'G v_k,
+    // D'u = z o (s \ u), and
+    //   J[k][j] = a_k.(dG_j x - dh_j) - z.(dG_j v_k)
+    // -- imp_grad_prim's shape with the weights a_k and v_k in vimp.  The NT form of the
+    // implicit gradient mode (D = W^-2) is exact for alpha's row to first order only; on the
+    // contact rows it is O(1) off whenever a SOC block is active, hence this linearisation.
+    //
+    // H' = P'L U by Gaussian elimination with partial pivoting, fully unrolled: the pivot row
+    // reaches position j by compare / select exchanges (no runtime-indexed register array),
+    // pr[] tracks the exchanged rows.  Replicated in every lane of the group (H is group-summed,
+    // so the lanes hold the same bits and take the same exchanges).
+    struct JacLU {
+        double A[N][N];   // unit-lower L below the diagonal, U on and above it
+        double ip[N];     // 1 / U[j][j]
+        int pr[N];        // row of H' at position j
+    };
+    // Dense rows only: a padded row of a dense SOC block (a cone's 4th coordinate, an inert
+    // slot) carries a zero G row, and an inert slot is masked besides, so neither adds to H.
+    // False if a pivot is zero or not finite.
+    DCOL_HD bool jacobian_factor(JacLU& F) const {
+        static_assert(!BALL && !CONE && !PART && !BOX && !SPLIT, "the Jacobian runs the dense rows");
+        double Hm[N][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = 0; c < N; ++c) Hm[j][c] = 0.0;
+#pragma unroll
+        for (int k = 0; k < OR; ++k) {   // orthant rows: symmetric, the upper triangle
+            const double d = vort(k) ? z[k] * frcp(s[k]) : 0.0;
+            double g[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) g[j] = gr(k, j) * d;
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+#pragma unroll
+                for (int c = j; c < N; ++c) Hm[j][c] += g[j] * gr(k, c);
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = 0; c < j; ++c) Hm[j][c] = Hm[c][j];
+#pragma unroll
+        for (int b = 0; b < SS; ++b) {   // SOC blocks: column c of D G_b, then G_b' of it
+            const int k0 = OR + SD * b;
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                double col[SD], zc[SD], t[SD];
+#pragma unroll
+                for (int e = 0; e < SD; ++e) col[e] = gr(k0 + e, c);
+                cprod(z + k0, col, zc);
+                ciprod(s + k0, zc, t);
+#pragma unroll
+                for (int e = 0; e < SD; ++e) {
+                    const double te = vs[b] ? t[e] : 0.0;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) Hm[j][c] += gr(k0 + e, j) * te;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = 0; c < N; ++c) F.A[c][j] = R::sum(Hm[j][c]);   // A = H'
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < N; ++j) F.pr[j] = j;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+#pragma unroll
+            for (int r = j + 1; r < N; ++r) {   // the largest |A[r][j]|, r >= j, into row j
+                const bool sw = fabs(F.A[r][j]) > fabs(F.A[j][j]);
+#pragma unroll
+                for (int c = 0; c < N; ++c) {
+                    const double a = F.A[j][c], b = F.A[r][c];
+                    F.A[j][c] = sw ? b : a;
+                    F.A[r][c] = sw ? a : b;
+                }
+                const int pa = F.pr[j], pb = F.pr[r];
+                F.pr[j] = sw ? pb : pa;
+                F.pr[r] = sw ? pa : pb;
+            }
+            const double p = F.A[j][j];
+            ok = ok && pos_finite(fabs(p));
+            F.ip[j] = frcp(p);
+#pragma unroll
+            for (int r = j + 1; r < N; ++r) {
+                const double l = F.A[r][j] * F.ip[j];
+                F.A[r][j] = l;
+#pragma unroll
+                for (int c = j + 1; c < N; ++c) F.A[r][c] -= l * F.A[j][c];
+            }
+        }
+        return ok;
+    }
+    // Output row k: v_k = H^-T e_k into vimp (L U v = P e_k) and the per-row weights
+    // a_k = -D'G v_k into wts (lane rows, like z)
+    DCOL_HD void jacobian_adjoints(const JacLU& F, int k, double* wts) {
+        double y[N];
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+            double t = (F.pr[r] == k) ? 1.0 : 0.0;
+#pragma unroll
+            for (int c = 0; c < r; ++c) t -= F.A[r][c] * y[c];
+            y[r] = t;
+        }
+#pragma unroll
+        for (int r = N - 1; r >= 0; --r) {
+            double t = y[r];
+#pragma unroll
+            for (int c = r + 1; c < N; ++c) t -= F.A[r][c] * vimp[c];
+            vimp[r] = t * F.ip[r];
+        }
+#pragma unroll
+        for (int i = 0; i < OR; ++i) {
+            const double d = vort(i) ? z[i] * frcp(s[i]) : 0.0;
+            wts[i] = -(d * rowdot(i, vimp));
+        }
+#pragma unroll
+        for (int b = 0; b < SS; ++b) {
+            const int k0 = OR + SD * b;
+            double u[SD], su[SD], t[SD];
+#pragma unroll
+            for (int e = 0; e < SD; ++e) u[e] = rowdot(k0 + e, vimp);
+            ciprod(s + k0, u, su);
+            cprod(z + k0, su, t);
+#pragma unroll
+            for (int e = 0; e < SD; ++e) wts[k0 + e] = vs[b] ? -t[e] : 0.0;
+        }
+    }
 };
 
 // ------------------------------------------------------------------------------------
@@ -2398,8 +2541,10 @@ DCOL_HD void launder(P& p) {
 // FDONLY: the copy built for the reference's FD gradient mode alone (launched only for runs
 // without DCOL_GRAD_ENVELOPE / DCOL_GRAD_IMPLICIT): the envelope and implicit code is not
 // compiled in, so its register pressure never shapes the FD path (variants.py BOX_FD)
+// JAC: the copy that can also write the contact-point Jacobian (KArgs::jac, F_JAC; dense rows,
+// variants.py JAC); every other copy compiles none of it
 template <int N, int NSOC, int OMAX, int LPP, bool FULL = false, bool BALL = false, bool CONE = false, int OE = 0,
-          int MODE = 0, bool GLDS = false, bool BOX = false, bool FDONLY = false, bool SPLIT = false>
+          int MODE = 0, bool GLDS = false, bool BOX = false, bool FDONLY = false, bool SPLIT = false, bool JAC = false>
 DCOL_HD void solve_one(const KArgs& A, int64_t pi, int q, int64_t ci = -1, int k1o = -1, int k2o = -1,
                        int32_t hs = -1) {
     DCOL_STAMP(A, pi, q, 0);
@@ -2547,6 +2692,92 @@ DCOL_HD void solve_one(const KArgs& A, int64_t pi, int q, int64_t ci = -1, int k
             for (int c = 6; c < 12; ++c) {
                 if (A.grad) A.grad[c * B + pi] = g[c];
                 if (rec) rec[1 + c] = g[c];
+            }
+        }
+    }
+    if constexpr (JAC) {
+        // The contact-point Jacobian, a phase of its own after the gradient's (same boundary
+        // rule: poses and records are re-read, nothing of this phase is live in the PDIP loop).
+        // The four output rows run one after another -- only the LU factor is held across them
+        // -- and within a row the lanes split as the gradient does: lane
+        // q & 1 of a 2+-lane group differentiates primitive q & 1, a one-lane group both in turn.
+        if ((A.flags & F_JAC) && A.jac) {
+            static_assert(MODE == 0 && !GLDS && !FDONLY, "JAC: one-launch dense copies");
+            asm volatile("" ::: "memory");
+            KArgs L = A;
+            launder(L.shapes);
+            launder(L.pose1);
+            launder(L.pose2);
+            const DevShape& T1 = L.shapes[k1];
+            const DevShape& T2 = L.shapes[k2];
+            constexpr int NP = LPP >= 2 ? 1 : 2;
+            const bool store = LPP >= 2 ? q < 2 : true;
+            bool fine = false;
+            if (ok) {
+                using Agg = typename Slv::LagAgg;
+                typename Slv::JacLU F;
+                fine = P.jacobian_factor(F);
+                if (fine) {
+#pragma unroll 1
+                    for (int k = 0; k < 4; ++k) {
+                        // (the z aggregates and the poses are formed again in every row: held
+                        // across the rows they cost 28 doubles of registers beside the factor,
+                        // and the allocator then spilled solver state inside the PDIP loop)
+                        Agg agA0, agA1;
+                        {
+                            double wts[Slv::M];
+                            P.jacobian_adjoints(F, k, wts);
+                            agA0 = P.lag_aggregate(T1, 0, wts);
+                            agA1 = P.lag_aggregate(T2, 1, wts);
+                        }
+                        const Agg ag0 = P.lag_aggregate(T1, 0);
+                        const Agg ag1 = P.lag_aggregate(T2, 1);
+                        launder(L.pose1);
+                        launder(L.pose2);
+                        double tj1[6], tj2[6];
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) {
+                            tj1[c] = L.pose1[c * B + pi];
+                            tj2[c] = L.pose2[c * B + pi];
+                        }
+#pragma unroll
+                        for (int pp = 0; pp < NP; ++pp) {
+                            const int prim = LPP >= 2 ? (q & 1) : pp;
+                            const DevShape& T = prim ? T2 : T1;
+                            Agg ag, agA;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                ag.u[c] = prim ? ag1.u[c] : ag0.u[c];
+                                agA.u[c] = prim ? agA1.u[c] : agA0.u[c];
+                            }
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                ag.zs[c] = prim ? ag1.zs[c] : ag0.zs[c];
+                                agA.zs[c] = prim ? agA1.zs[c] : agA0.zs[c];
+                            }
+                            ag.kind = prim ? ag1.kind : ag0.kind;
+                            agA.kind = ag.kind;
+                            double th[6], jr[6];
+#pragma unroll
+                            for (int c = 0; c < 6; ++c) th[c] = prim ? tj2[c] : tj1[c];
+                            P.imp_grad_prim(agA, ag, T, prim, th, jr);
+                            if (store) {
+#pragma unroll
+                                for (int c = 0; c < 6; ++c) A.jac[(int64_t)(12 * k + 6 * prim + c) * B + pi] = jr[c];
+                            }
+                        }
+                    }
+                }
+            }
+            if (!fine && store) {   // status not OK, or a zero / non-finite pivot: NaN in all 48
+#pragma unroll 1
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int pp = 0; pp < NP; ++pp) {
+                        const int prim = LPP >= 2 ? (q & 1) : pp;
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) A.jac[(int64_t)(12 * k + 6 * prim + c) * B + pi] = nan;
+                    }
             }
         }
     }
@@ -2709,7 +2940,8 @@ __device__ __forceinline__ int32_t hint_wave_slot(const KArgs& A) {
 }
 #endif
 
-template <int N, int NSOC, int OMAX, int LPP, int WPS, int FL, int OE = 0>
+// JAC: the copy with the contact-point Jacobian phase (solve_one JAC; dcol_kernels_jac.hip)
+template <int N, int NSOC, int OMAX, int LPP, int WPS, int FL, int OE = 0, bool JAC = false>
 __global__ void __launch_bounds__(kSolveBlock, WPS % 10) prox_kernel(KArgs A) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t slot = t / LPP;
@@ -2727,7 +2959,7 @@ __global__ void __launch_bounds__(kSolveBlock, WPS % 10) prox_kernel(KArgs A) {
     if (slot >= A.n) return;
     const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
     solve_one<N, NSOC, OMAX, LPP, (FL & 1) != 0, (FL & 2) != 0, (FL & 4) != 0, OE, (FL & 16) ? 1 : 0,
-              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0>(A, pi, q, -1, -1, -1, hs);
+              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0, JAC>(A, pi, q, -1, -1, -1, hs);
 }
 
 // The resume launch of a suspend / resume pair: one lane group per continuation entry;

@@ -83,6 +83,16 @@ inline int choose_lpp(int N, int nsoc, int omax, int fl = 0) {
     return (first == 0 && fl != 0) ? choose_lpp(N, nsoc, omax, 0) : first;   // no copies of the flavour: dense
 }
 
+// lanes per pair of a shape's contact-point Jacobian copy (DCOL_JAC_VARIANTS: one per shape,
+// the dense kernel's first listed LPP; DCOL_LPP does not apply), 0 if the shape has none
+inline int jac_lpp(int N, int nsoc, int omax) {
+#define DCOL_JL(NN, NS, OM, LP, WP, FL) \
+    if (NN == N && NS == nsoc && OM == omax) return LP;
+    DCOL_JAC_VARIANTS(DCOL_JL)
+#undef DCOL_JL
+    return 0;
+}
+
 // A row pool starts with one zero row (index 0; every shape's rows follow): a lane slot
 // without a row of its pair loads that row instead of branching around its loads (the
 // kernels' orth_row / ext_row), so all slots' loads issue back to back.

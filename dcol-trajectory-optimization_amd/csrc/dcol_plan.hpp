@@ -189,6 +189,10 @@ struct BucketMode {
     // bucket as a plan that fills the GPU (throughput configurations: the packed launch of a
     // small plan the fused kernel cannot take)
     bool force_large = false;
+    // DCOL_PLAN_JACOBIAN: every pair on the dense-row kernels (no row partition, no ball /
+    // cone / box form, whatever the policy says) at the lanes per pair of its shape's
+    // Jacobian copy (jac_lpp); set together with force_large (plan_layout_jac)
+    bool jac = false;
 };
 
 // A launch too small to fill the GPU runs the configuration with the shortest per-pair
@@ -279,7 +283,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
     auto classify_pair = [&](int32_t i1, int32_t i2) -> int32_t {
         const DevShape& a = shapes[i1];
         const DevShape& b = shapes[i2];
-        PairClass c = classify(a, b, mode.case4);
+        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false) : classify(a, b, mode.case4);
+        if (mode.jac && c.status == DCOL_OK) c.lpp = jac_lpp(c.N, c.nsoc, c.omax);
         const bool none_cone = a.soc_kind != SOC_CONE && b.soc_kind != SOC_CONE;
         const bool all_cone = a.soc_kind != SOC_BALL && b.soc_kind != SOC_BALL;
         if (mode.fused_part && c.status == DCOL_OK && c.oe > 0 &&
@@ -288,7 +293,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
             c = classify(a, b, mode.case4, /*part=*/false);
         if (mode.lat_part && c.status == DCOL_OK && c.oe > 0 && part_lpp(c.N, c.nsoc, c.omax, c.oe, /*latency=*/true) < 2)
             c = classify(a, b, mode.case4, /*part=*/false);
-        const SocForm soc = c.nsoc == 0 ? ((a.boxp && b.boxp && c.N == 4 && c.omax == 12 && c.o == 12 && !pol.no_box)
+        const SocForm soc = mode.jac ? SocForm::Dense
+                            : c.nsoc == 0 ? ((a.boxp && b.boxp && c.N == 4 && c.omax == 12 && c.o == 12 && !pol.no_box)
                                                ? SocForm::Box : SocForm::Dense)
                             : (none_cone && !pol.no_ball) ? SocForm::Ball
                             : (all_cone && c.N == 4 && !pol.no_cone) ? SocForm::Cone : SocForm::Dense;
@@ -498,6 +504,23 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
         }
     }
     return DCOL_SUCCESS;
+}
+
+// The layout of a DCOL_PLAN_JACOBIAN plan: the pairs bucketed on the dense-row kernels
+// (BucketMode::jac), one launch per bucket over the streams of a plan that fills the GPU --
+// never fused or packed, no latency configurations (the Jacobian copies exist at one lane
+// count per shape).
+inline int plan_layout_jac(const std::vector<DevShape>& shapes, int simds, int64_t B, const int32_t* s1,
+                           const int32_t* s2, bool case4, const PlanPolicy& pol, PlanLayout& out) {
+    BucketMode mode;
+    mode.case4 = case4;
+    mode.force_large = true;
+    mode.jac = true;
+    const int rc = bucket_pairs(shapes, simds, B, s1, s2, mode, pol, out);
+    // (bucketed as a large plan; whether it can fill the GPU still decides if a run asks a
+    // resident pair server to leave)
+    if (rc == DCOL_SUCCESS) out.small = solve_lanes(out).second < pol.small_lanes(simds);
+    return rc;
 }
 
 }  // namespace dcol_host

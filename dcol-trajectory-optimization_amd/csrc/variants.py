@@ -51,6 +51,7 @@ Generates dcol_variants.inc (FL = variant flags: bit 0 FULL, bit 1 BALL, bit 2 C
   DCOL_SUSP_VARIANTS(X)  X(N, NSOC, OMAX, LPP, WPS, FL, OE) suspend / resume copies (FL bit 4 = 16)
   DCOL_SPLIT_VARIANTS(X)  X(N, NSOC, OMAX, LPP, WPS, FL, OE) split-SOC PART copies (FL bit 5 = 32)
   DCOL_PACKED_VARIANTS(X)  X(ID, N, NSOC, OMAX, LPP, FL, OE) the cases of the packed kernel
+  DCOL_JAC_VARIANTS(X)  X(N, NSOC, OMAX, LPP, WPS, 0) the contact-point Jacobian copies (jac())
 
 SUSP variants (dcol_device.hpp KArgs susp_*, dcol_kernels_susp.hip): a large launch runs as a
 main launch in which a wave hands its last few iterating pairs (<= DCOL_SUSPEND_T of 32, after
@@ -337,6 +338,14 @@ def packed():
     return out
 
 
+def jac(shapes):
+    """JAC copies (dcol_device.hpp solve_one JAC, dcol_kernels_jac.hip): the dense-row kernel
+    with the contact-point Jacobian phase, one per shape at the shape's first listed LPP and
+    one wave per SIMD.  The dense kernel solves any pair of its (N, NSOC, OMAX), so the
+    structured flavours have no twins; a DCOL_PLAN_JACOBIAN plan buckets on dense rows."""
+    return [(n, s, o, configs(n, s, o)[0][0], 1) for n, s, o in shapes]
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     shapes = [(n, s, o) for (n, s), os_ in sorted(OMAX.items()) for o in os_]
@@ -372,6 +381,8 @@ def main():
     lines += [f"    X({i}, {n}, {s}, {o}, {l}, {fl}, {oe}) \\" for i, (n, s, o, l, fl, oe) in enumerate(packed())]
     lines += ["", "#define DCOL_SPLIT_VARIANTS(X) \\"]
     lines += [f"    X({n}, {s}, {o}, {l}, {w}, {fl}, {oe}) \\" for n, s, o, l, w, fl, oe in SPLIT]
+    lines += ["", "#define DCOL_JAC_VARIANTS(X) \\"]
+    lines += [f"    X({n}, {s}, {o}, {l}, {w}, 0) \\" for n, s, o, l, w in jac(shapes)]
     lines += ["", "#define DCOL_SUSP_VARIANTS(X) \\"]
     lines += [f"    X({n}, {s}, {o}, {l}, {w}, {fl | 16}, {oe}) \\" for n, s, o, l, w, fl, oe in SUSP]
     lines.append("")

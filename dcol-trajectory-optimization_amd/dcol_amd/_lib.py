@@ -18,12 +18,12 @@ POLYTOPE, SPHERE, CONE, CAPSULE, CYLINDER, POLYGON = range(6)
 # enum dcol_status
 OK, MAXITER, UNSUPPORTED, NOT_PD, NONFINITE, TOO_LARGE = range(6)
 # enum dcol_flags
-GRAD_FD, GRAD_ENVELOPE, CONTACT, CASE4, GRAD_IMPLICIT, NO_GATHER = 1, 2, 4, 8, 16, 32
+GRAD_FD, GRAD_ENVELOPE, CONTACT, CASE4, GRAD_IMPLICIT, NO_GATHER, JACOBIAN = 1, 2, 4, 8, 16, 32, 64
 GRAD_ANY = GRAD_FD | GRAD_ENVELOPE | GRAD_IMPLICIT
 # enum dcol_plan_options
-PLAN_CASE4, PLAN_NO_FUSE, PLAN_SUSPEND = 1, 2, 4
+PLAN_CASE4, PLAN_NO_FUSE, PLAN_SUSPEND, PLAN_JACOBIAN = 1, 2, 4, 8
 SUCCESS, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3
-ABI_VERSION = 4
+ABI_VERSION = 5
 PAIR_PLANS_MAX = 64   # DCOL_PAIR_PLANS_MAX
 
 
@@ -60,6 +60,11 @@ SIGNATURES = {
     "dcol_plan_suspended": (c_int, [c_void_p, POINTER(c_int64)]),
     "dcol_plan_run": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dcol_plan_run_jac": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dcol_prox_jacobian_host": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                        c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "dcol_prox_batch_host": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                      c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dcol_prox_pair": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_double, c_int32, c_int32, c_void_p,

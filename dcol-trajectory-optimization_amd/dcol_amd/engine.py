@@ -71,6 +71,9 @@ class Result:
     grad: np.ndarray | None
     iters: np.ndarray
     status: np.ndarray
+    # (B, 4, 12) contact-point Jacobian d[x0, x1, x2, alpha] / d[r1, p1, r2, p2] of
+    # solve_host(jacobian=True), else None; NaN rows: see include/dcol.h dcol_plan_run_jac
+    jac: np.ndarray | None = None
 
 
 class Table:
@@ -105,12 +108,15 @@ class Table:
 class Plan:
     """Owning wrapper of a dcol_plan: a fixed pairing bucketed by kernel variant."""
 
-    def __init__(self, table: Table, s1, s2, case4: bool = False, fuse: bool = True, suspend: bool = False):
+    def __init__(self, table: Table, s1, s2, case4: bool = False, fuse: bool = True, suspend: bool = False,
+                 jacobian: bool = False):
         """case4=True: solve case-4 pairs (DCOL_PLAN_CASE4 extension) instead of reporting
         UNSUPPORTED like the reference.  fuse=False: one launch per variant bucket even for
         a small mixed plan (DCOL_PLAN_NO_FUSE; A/B and tests).  suspend=True: large buckets
         run as a suspend / resume launch pair (DCOL_PLAN_SUSPEND; bitwise the same results;
-        the plan owns scratch -- do not run it on two streams at once)."""
+        the plan owns scratch -- do not run it on two streams at once).  jacobian=True: the plan
+        can run(jacobian=True) (DCOL_PLAN_JACOBIAN: dense-row buckets, one launch each; not
+        with suspend)."""
         lib = _lib.load()
         self.s1 = np.ascontiguousarray(s1, dtype=np.int32)
         self.s2 = np.ascontiguousarray(s2, dtype=np.int32)
@@ -120,8 +126,9 @@ class Plan:
         self.B = int(self.s1.size)
         h = ctypes.c_void_p()
         self.case4 = bool(case4)
+        self.jacobian = bool(jacobian)
         opts = (_lib.PLAN_CASE4 if case4 else 0) | (0 if fuse else _lib.PLAN_NO_FUSE) | (
-            _lib.PLAN_SUSPEND if suspend else 0)
+            _lib.PLAN_SUSPEND if suspend else 0) | (_lib.PLAN_JACOBIAN if jacobian else 0)
         _lib.check(lib.dcol_plan_create_ex(table.handle, self.B, _np_ptr(self.s1), _np_ptr(self.s2),
                                            opts, ctypes.byref(h)), "dcol_plan_create_ex")
         self.handle = h
@@ -160,11 +167,13 @@ class Plan:
         return int(n.value)
 
     def run(self, pose1, pose2, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, grad="fd", contact=True,
-            out=None, stream=None):
+            out=None, stream=None, jacobian=False):
         """Solve on the device.  pose1/pose2: torch float64 tensors [6, B] on the table's
         device (structure of arrays).  Returns dict of torch tensors (alpha [B],
         contact [3, B], grad [12, B], iters [B], status [B]); asynchronous on `stream`
-        (torch stream or None = current stream)."""
+        (torch stream or None = current stream).  jacobian=True (a plan made with
+        jacobian=True): also out["jac"], [48, B] -- row 12 k + j = d(x, y, z of the contact
+        point, alpha)[k] / d(r1, p1, r2, p2)[j] (dcol_plan_run_jac)."""
         import torch
         B = self.B
         dev = torch.device("cuda", self.table.device)
@@ -173,10 +182,18 @@ class Plan:
                 raise ValueError(f"poses must be contiguous float64 [6, {B}] on {dev}")
         flags = grad_flag(grad) | (_lib.CONTACT if contact else 0)
         if out is None:
-            out = alloc_outputs(B, dev, bool(flags & _lib.GRAD_ANY), bool(contact))
+            out = alloc_outputs(B, dev, bool(flags & _lib.GRAD_ANY), bool(contact), want_jac=bool(jacobian))
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        if jacobian:
+            if "jac" not in out:
+                raise ValueError("out has no 'jac' buffer")
+            _lib.check(_lib.load().dcol_plan_run_jac(
+                self.handle, ptr(pose1), ptr(pose2), float(tol), int(max_iter), flags | _lib.JACOBIAN,
+                ptr(out["alpha"]), ptr(out.get("contact")), ptr(out.get("grad")), ptr(out["jac"]),
+                ptr(out["iters"]), ptr(out["status"]), ctypes.c_void_p(stream.cuda_stream)), "dcol_plan_run_jac")
+            return out
         _lib.check(_lib.load().dcol_plan_run(self.handle, ptr(pose1), ptr(pose2), float(tol), int(max_iter), flags,
                                              ptr(out["alpha"]), ptr(out.get("contact")), ptr(out.get("grad")),
                                              ptr(out["iters"]), ptr(out["status"]), ctypes.c_void_p(stream.cuda_stream)),
@@ -226,7 +243,7 @@ class Plan:
             self.handle = None
 
 
-def alloc_outputs(B: int, device, want_grad=True, want_contact=True):
+def alloc_outputs(B: int, device, want_grad=True, want_contact=True, *, want_jac=False):
     import torch
     out = {"alpha": torch.empty(B, dtype=torch.float64, device=device),
            "iters": torch.empty(B, dtype=torch.int32, device=device),
@@ -235,6 +252,8 @@ def alloc_outputs(B: int, device, want_grad=True, want_contact=True):
         out["contact"] = torch.empty((3, B), dtype=torch.float64, device=device)
     if want_grad:
         out["grad"] = torch.empty((12, B), dtype=torch.float64, device=device)
+    if want_jac:
+        out["jac"] = torch.empty((48, B), dtype=torch.float64, device=device)
     return out
 
 
@@ -309,16 +328,16 @@ class Engine:
                 self._table = Table(self._specs, self.device)
             return self._table
 
-    def plan(self, s1, s2, cache=True, case4=False, fuse=True, suspend=False) -> Plan:
+    def plan(self, s1, s2, cache=True, case4=False, fuse=True, suspend=False, jacobian=False) -> Plan:
         s1 = np.ascontiguousarray(s1, dtype=np.int32)
         s2 = np.ascontiguousarray(s2, dtype=np.int32)
         if not cache or suspend:   # suspend plans own scratch: never shared through the cache
-            return Plan(self.table, s1, s2, case4, fuse, suspend)
-        key = (s1.tobytes(), s2.tobytes(), bool(case4), bool(fuse))
+            return Plan(self.table, s1, s2, case4, fuse, suspend, jacobian)
+        key = (s1.tobytes(), s2.tobytes(), bool(case4), bool(fuse), bool(jacobian))
         with self._lock:
             p = self._plans.get(key)
             if p is None or p.table is not self.table:
-                p = Plan(self.table, s1, s2, case4, fuse)
+                p = Plan(self.table, s1, s2, case4, fuse, jacobian=jacobian)
                 self._plans[key] = p
                 if len(self._plans) > 32:
                     self._plans.popitem(last=False)
@@ -328,9 +347,10 @@ class Engine:
 
     # ---------------------------------------------------------------- solves
     def solve_host(self, s1, s2, pose1, pose2, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, grad="fd",
-                   contact=True, case4=False) -> Result:
+                   contact=True, case4=False, jacobian=False) -> Result:
         """Host arrays in/out: s1, s2 int [B]; pose1, pose2 float64 [B, 6] (r, p).
-        case4=True: the DCOL_CASE4 extension (see Plan)."""
+        case4=True: the DCOL_CASE4 extension (see Plan).  jacobian=True: also Result.jac,
+        (B, 4, 12), the contact-point Jacobian (dcol_prox_jacobian_host)."""
         s1 = np.ascontiguousarray(s1, dtype=np.int32).reshape(-1)
         s2 = np.ascontiguousarray(s2, dtype=np.int32).reshape(-1)
         B = s1.size
@@ -343,6 +363,13 @@ class Engine:
         iters = np.empty(B, dtype=np.int32)
         status = np.empty(B, dtype=np.int32)
         table = self.table
+        if jacobian:
+            jac = np.empty((B, 4, 12))
+            _lib.check(_lib.load().dcol_prox_jacobian_host(
+                table.handle, B, _np_ptr(s1), _np_ptr(s2), _np_ptr(p1), _np_ptr(p2), float(tol), int(max_iter), flags,
+                _np_ptr(alpha), _np_ptr(cp), _np_ptr(g), _np_ptr(jac), _np_ptr(iters), _np_ptr(status)),
+                "dcol_prox_jacobian_host")
+            return Result(alpha, cp, g, iters, status, jac)
         _lib.check(_lib.load().dcol_prox_batch_host(table.handle, B, _np_ptr(s1), _np_ptr(s2), _np_ptr(p1), _np_ptr(p2),
                                                     float(tol), int(max_iter), flags, _np_ptr(alpha), _np_ptr(cp),
                                                     _np_ptr(g), _np_ptr(iters), _np_ptr(status)),

@@ -37,12 +37,14 @@
 extern "C" {
 #endif
 
-#define DCOL_ABI_VERSION 4   /* 2: 14-slot multi-GPU record (status / iters as an int32 pair);
+#define DCOL_ABI_VERSION 5   /* 2: 14-slot multi-GPU record (status / iters as an int32 pair);
                                 3: DCOL_NO_GATHER + dcol_comm_all_gather, dcol_table_pair_plans,
                                    dcol_table_pair_stats;
                                 4: dcol_plan_num_streams, dcol_plan_launch_form, dcol_shutdown,
                                    dcol_table_stop_pair_server, dcol_table_pair_server_running,
-                                   dcol_debug_pair_stamps */
+                                   dcol_debug_pair_stamps;
+                                5: the contact-point Jacobian: DCOL_PLAN_JACOBIAN, DCOL_JACOBIAN,
+                                   dcol_plan_run_jac, dcol_prox_jacobian_host */
 
 /* Primitive types (misc_primitive_constructor.py:4-88). */
 enum dcol_shape_type {
@@ -79,12 +81,16 @@ enum dcol_flags {
                                PDIP's normal matrix G'W^-2 G (same Cholesky routine), for
                                the 12 pose coordinates; equals the envelope gradient as
                                mu -> 0 (pdip.py:434; no reference counterpart)            */
-    DCOL_NO_GATHER = 32     /* dcol_prox_batch_multi_gpu in place only: the solve and the
+    DCOL_NO_GATHER = 32,    /* dcol_prox_batch_multi_gpu in place only: the solve and the
                                record writes of the call (this rank's rows of rec_all and
                                their NaN tail) WITHOUT the all-gather -- issue it with
                                dcol_comm_all_gather (e.g. on a stream of its own, so the
                                next step's solve overlaps it), or time the step without
                                its collective (comm = step - this, like for like)         */
+    DCOL_JACOBIAN = 64      /* dcol_plan_run_jac / dcol_prox_jacobian_host only: write the
+                               contact-point Jacobian d[x0,x1,x2,alpha] / d[r1,p1,r2,p2]
+                               (DifferentiableCollisions.jl proximity_jacobian; see
+                               dcol_plan_run_jac).  Independent of the gradient flags.      */
 };
 #define DCOL_GRAD_ANY (DCOL_GRAD_FD | DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)
 
@@ -100,12 +106,18 @@ enum dcol_plan_options {
                            buckets (kernel variants) whose pairs together fill less than one
                            wave per SIMD -- an ALTRO phase batch -- runs every bucket in ONE
                            fused launch (no stream fan-out); results are bitwise the same.  */
-    DCOL_PLAN_SUSPEND = 4 /* large buckets with a suspend / resume kernel pair run as a main
+    DCOL_PLAN_SUSPEND = 4, /* large buckets with a suspend / resume kernel pair run as a main
                            launch in which each wave hands its last few iterating pairs to a
                            compact resume launch, instead of idling most of its lanes until
                            its slowest pair converges; results are bitwise the same.  The plan
                            then owns device scratch written by every run: do not run it on
                            two streams at once (one plan per stream).                       */
+    DCOL_PLAN_JACOBIAN = 8 /* the plan can run dcol_plan_run_jac with DCOL_JACOBIAN: its pairs
+                           are bucketed on the dense-row kernels (as under DCOL_NO_BALL / NO_CONE /
+                           NO_PART / NO_BOX), each bucket at its shape's first lane count, and
+                           it always takes the DCOL_FORM_BUCKETS form -- no fused or packed
+                           launch, no suspend / resume, no order hint.  Not with
+                           DCOL_PLAN_SUSPEND (DCOL_ERR_ARG).                                */
 };
 
 /* Return codes of every entry point. */
@@ -205,6 +217,38 @@ int dcol_plan_suspended(const dcol_plan* plan, int64_t* n);
 int dcol_plan_run(const dcol_plan* plan, const double* pose1, const double* pose2, double tol,
                   int32_t max_iter, int32_t flags, double* alpha, double* contact, double* grad,
                   int32_t* iters, int32_t* status, void* stream);
+
+/* dcol_plan_run plus, with DCOL_JACOBIAN in flags, the contact-point Jacobian
+ *   jac          : [4][12][B]  component (k, j) at (12 k + j) B + i: row k = x, y, z of the
+ *                              contact point x[0:3] and alpha, column j = r1, p1, r2, p2
+ * (DEVICE pointer, structure-of-arrays like the rest).  It is the derivative of the returned
+ * iterate: the KKT conditions G'z + c = 0, G x + s = h, s o z = const differentiated in the
+ * pose with the residuals held fixed, L(z) ds + L(s) dz = 0 with the cones' arrow matrices
+ * (NOT the NT-scaled form of DCOL_GRAD_IMPLICIT, which is only first-order exact for alpha):
+ * H dx = -dG'z - G'D (dG x - dh), D = L(s)^-1 L(z), H = G'D G, solved by an LU with partial
+ * pivoting per pair.  Row 3 is another evaluation of d alpha / d pose.
+ *   - a pair whose status is not DCOL_OK gets NaN in all 48 entries;
+ *   - a pair whose H meets a zero or non-finite pivot gets NaN in all 48 and KEEPS its status
+ *     (DCOL_OK): alpha, contact and grad of that pair are valid, the Jacobian is not defined
+ *     at its iterate (check jac for NaN).
+ * Where the contact point is not unique (face-to-face boxes) H is near-singular and the
+ * entries are large and meaningless, as the derivative itself is.
+ * The plan must have been made with DCOL_PLAN_JACOBIAN, and jac must not be NULL: else
+ * DCOL_ERR_ARG (message in dcol_last_error).  The gradient flags are independent: grad is
+ * written in whichever mode is asked.  Without DCOL_JACOBIAN the call is dcol_plan_run (jac
+ * ignored).  Asynchronous, capturable and allocation-free like dcol_plan_run.            */
+int dcol_plan_run_jac(const dcol_plan* plan, const double* pose1, const double* pose2, double tol,
+                      int32_t max_iter, int32_t flags, double* alpha, double* contact, double* grad,
+                      double* jac, int32_t* iters, int32_t* status, void* stream);
+/* Host form of the same: HOST array-of-structures arrays in and out like
+ * dcol_prox_batch_host, jac B x 4 x 12 (required); DCOL_JACOBIAN is implied.  Builds a
+ * transient DCOL_PLAN_JACOBIAN plan (with DCOL_CASE4 in flags: plus DCOL_PLAN_CASE4).
+ * Synchronous; calls on one table are serialised.                                         */
+int dcol_prox_jacobian_host(const dcol_table* table, int64_t B, const int32_t* shape1,
+                            const int32_t* shape2, const double* pose1, const double* pose2,
+                            double tol, int32_t max_iter, int32_t flags, double* alpha,
+                            double* contact, double* grad, double* jac, int32_t* iters,
+                            int32_t* status);
 
 /* Convenience: HOST arrays in, HOST arrays out, synchronous.  Array-of-structures rows:
  * pose1/pose2 B x 6, contact B x 3, grad B x 12.  Builds a transient plan; staging

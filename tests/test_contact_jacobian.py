@@ -1,0 +1,497 @@
+"""The contact-point Jacobian d[x0, x1, x2, alpha] / d[r1, p1, r2, p2] (DCOL_JACOBIAN,
+dcol_plan_run_jac, Engine.solve_host(jacobian=True), proximity_jacobian; DESIGN.md "gradient
+modes").
+
+Three layers, each checked against the one before:
+  truth        central differences of x*[0:4] solved to mu < 1e-11 (the oracle's PDIP);
+  restatement  tests/contact_jacobian_ref.py: the exact-complementarity linearisation at the
+               returned iterate, on the oracle's own pieces (NumPy, pivoted solve);
+  kernel       the JAC copies of the HIP solver, emulated on x86 (tests/emul_jac) and on the GPU.
+
+Pairs are sampled as test_implicit_grad._pairs does (status-0 pairs, np.linspace indices);
+sc = max(|ref|_inf over the 4 x 12, 1).  scene_piano is left out of the truth comparison (its
+box x box contacts are face-to-face: the contact point is not unique and its derivative does
+not exist), edge_cases out of the numeric comparisons (a 1e-13 relative perturbation of its
+iterates moves J by 1.6e-4) and used for the failure checks.
+
+Kernel-against-restatement rule (tests 2, 5, 6, 8).  The tolerance of a pair comes from the
+restatement alone: sens = the largest change of J over three seeded re-evaluations with x, s,
+z each perturbed by 1e-13 relative; tolerance = max(1e-7, 100 sens) sc, never above 1e-3 sc
+(beyond that the comparison could no longer tell this formula from the NT form).  Every
+sampled pair is compared.  A pair whose restatement has cond(H) > 1e10 may miss its tolerance
+-- H is then singular to working precision and two correct evaluations need not agree --
+but at most 3 pairs of a set may be excused that way; a pair with cond(H) <= 1e10 must meet
+it.  (Measured on 40 pairs per set: cond(H) > 1e10 on 7 pairs of scene_cone and none of the
+other four sets, its largest among the others 2.7e9; all 200 pairs meet their tolerance, the
+worst at 0.03 of it, so no pair is excused.  The rule as first proposed left pairs with
+cond(H) > 1e10 out of the comparison and allowed 3 of 40 to be left out, from a count of 1 in 24
+on scene_cone; at 40 pairs 7 are above 1e10, so they are compared instead and only a miss is
+capped -- no less is asked of any pair.)
+"""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import PKG, REPO, alpha_close, golden_files, load_golden
+from contact_jacobian_ref import contact_jacobian, tolerance
+
+GOLD = {p.split("/")[-1][:-4]: p for p in golden_files()}
+SETS = ["scene_quad", "scene_cone", "synthetic_mixed", "synthetic_polypoly", "large_polytopes"]
+EMUL_DIR = os.path.join(REPO, "tests", "emul_jac")
+EMUL_LIB = os.path.join(EMUL_DIR, "libdcol_emul_jac.so")
+HEADER = os.path.join(REPO, "include", "dcol.h")
+COND_MAX = 1e10
+EXCUSED_MAX = 3
+
+
+@functools.lru_cache(maxsize=None)
+def _golden(name):
+    return load_golden(GOLD[name])
+
+
+def _pairs(name, n):
+    d = _golden(name)
+    ok = np.flatnonzero(d["status"] == 0)
+    return d, ok[np.linspace(0, ok.size - 1, n).astype(int)]
+
+
+def _iterate(d, i, tol=None, case4=False):
+    from oracle import dcol_oracle as O
+    a, b = O.shape_from_table(d, d["s1"][i]), O.shape_from_table(d, d["s2"][i])
+    p1, p2 = d["pose1"][i], d["pose2"][i]
+    tol = float(d["tol"]) if tol is None else tol
+    _, _, x, s, z, _, dims = O.proximity(a, p1[:3], p1[3:], b, p2[:3], p2[3:], tol, case4)
+    return O, a, b, x, s, z, np.concatenate([p1, p2]), dims
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(name, i, case4=False):
+    """(J, cond(H), tolerance) of pair i of a golden set: computed once, shared by the tests"""
+    O, a, b, x, s, z, th, dims = _iterate(_golden(name), i, case4=case4)
+    J, cond = contact_jacobian(O, a, b, x, s, z, th, dims, case4)
+    J.setflags(write=False)
+    return J, cond, tolerance(O, a, b, x, s, z, th, dims, J, case4)
+
+
+def _check_against_restatement(name, idx, jac):
+    """The rule of the module docstring for the pairs idx of a set and their kernel results"""
+    excused = []
+    for j, i in enumerate(idx):
+        J, cond, tol = _restated(name, int(i))
+        err = np.abs(jac[j] - J).max()
+        sc = max(np.abs(J).max(), 1.0)
+        print(f"{name}[{i}]: err {err / sc:.2e} tol {tol / sc:.2e} cond(H) {cond:.1e}")
+        if err <= tol:     # (NaN fails)
+            continue
+        assert cond > COND_MAX, (name, i, err / sc, tol / sc, cond)
+        excused.append(int(i))
+    assert len(excused) <= EXCUSED_MAX, (name, excused)
+
+
+# ---------------------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------------------
+def _truth(O, a, b, th, step):
+    J = np.empty((4, 12))
+    for j in range(12):
+        tp, tm = th.copy(), th.copy()
+        tp[j] += step
+        tm[j] -= step
+        xp = O.proximity(a, tp[:3], tp[3:6], b, tp[6:9], tp[9:], 1e-11)[2][:4]
+        xm = O.proximity(a, tm[:3], tm[3:6], b, tm[6:9], tm[9:], 1e-11)[2][:4]
+        J[:, j] = (xp - xm) / (2 * step)
+    return J
+
+
+@pytest.mark.parametrize("name", SETS)
+def test_restatement_matches_true_derivative(name):
+    """The mathematics.  Truth: central differences, step 1e-5, of O.proximity(...)[2][:4]
+    solved at tol 1e-11.  A pair is well-posed if the truth at steps 1e-5 and 3e-5 agree within
+    1e-4 sc; at most 3 of 24 pairs per set may fail that.  The restatement at the golden
+    tolerance is within 1e-2 sc of the truth on the well-posed pairs.
+
+    Measured (24 pairs per set): pairs failing well-posedness / worst restatement error /
+    worst error of the NT form (D = W^-2, the implicit gradient mode's linearisation extended
+    to the contact rows; printed, not asserted) on the same pairs:
+      scene_quad          1   1.9e-4   4.7e+0
+      scene_cone          2   5.2e-3   4.7e+0
+      synthetic_mixed     0   1.2e-3   2.8e+0
+      synthetic_polypoly  0   2.1e-5   2.1e-5   (orthant rows only: the two forms coincide)
+      large_polytopes     0   2.2e-3   1.8e+0"""
+    d, idx = _pairs(name, 24)
+    ill, worst, worst_nt = [], 0.0, 0.0
+    for i in idx:
+        O, a, b, x, s, z, th, dims = _iterate(d, i)
+        T, T3 = _truth(O, a, b, th, 1e-5), _truth(O, a, b, th, 3e-5)
+        sc = max(np.abs(T).max(), 1.0)
+        if not np.abs(T - T3).max() <= 1e-4 * sc:
+            ill.append(int(i))
+            continue
+        J, _, _ = _restated(name, int(i))
+        Jn, _ = contact_jacobian(O, a, b, x, s, z, th, dims, nt=True)
+        err, err_nt = np.abs(J - T).max() / sc, np.abs(Jn - T).max() / sc
+        worst, worst_nt = max(worst, err), max(worst_nt, err_nt)
+        assert err <= 1e-2, (name, i, err)
+    print(f"{name}: ill-posed {len(ill)} of {idx.size}, worst restatement error {worst:.2e}, NT form {worst_nt:.2e}")
+    assert len(ill) <= 3, (name, ill)
+
+
+def emul_jac(d, idx, flags=4, max_iter=50, case4=False):
+    """Pairs idx of a golden-layout table through the x86 build of the JAC copies"""
+    from dcol_amd import make_descs, spec_from_arrays
+    if not os.path.exists(EMUL_LIB):   # (build() makes it; a bare checkout builds it here)
+        subprocess.run(["make", "-C", EMUL_DIR, "-j8", "-s"], check=True)
+    lib = ctypes.CDLL(EMUL_LIB)
+    P = ctypes.c_void_p
+    specs = [spec_from_arrays(d, k) for k in range(len(d["type"]))]
+    descs, keep = make_descs(specs)
+    B = len(idx)
+    s1 = np.ascontiguousarray(d["s1"][idx], np.int32)
+    s2 = np.ascontiguousarray(d["s2"][idx], np.int32)
+    p1 = np.ascontiguousarray(d["pose1"][idx])
+    p2 = np.ascontiguousarray(d["pose2"][idx])
+    al, ct, gr, jc = np.empty(B), np.empty((B, 3)), np.empty((B, 12)), np.empty((B, 4, 12))
+    it, st = np.empty(B, np.int32), np.empty(B, np.int32)
+    rc = lib.dcol_emul_jac_batch(descs, ctypes.c_int32(len(specs)), ctypes.c_int64(B), P(s1.ctypes.data),
+                                 P(s2.ctypes.data), P(p1.ctypes.data), P(p2.ctypes.data), ctypes.c_double(float(d["tol"])),
+                                 ctypes.c_int32(max_iter), ctypes.c_int32(flags), ctypes.c_int32(int(case4)),
+                                 P(al.ctypes.data), P(ct.ctypes.data), P(gr.ctypes.data), P(jc.ctypes.data),
+                                 P(it.ctypes.data), P(st.ctypes.data))
+    assert rc == 0
+    del keep
+    return al, ct, jc, it, st
+
+
+@functools.lru_cache(maxsize=None)
+def _emulated(name):
+    d, idx = _pairs(name, 40)
+    return idx, emul_jac(d, idx)
+
+
+@pytest.mark.parametrize("name", SETS)
+def test_emulated_kernel_matches_restatement(name):
+    """The kernel's Jacobian phase (x86 build, one lane per pair) against the restatement at
+    the same 40 pairs per set, under the rule of the module docstring."""
+    idx, (al, ct, jc, it, st) = _emulated(name)
+    d = _golden(name)
+    assert np.all(st == 0)
+    np.testing.assert_array_equal(it, d["iters"][idx])
+    assert np.all(alpha_close(al, d["alpha"][idx]))
+    # rows 0..2 differentiate the contact point the run returns, row 3 alpha
+    assert np.all(np.abs(ct - d["contact"][idx]) <= 1e-6 * np.maximum(np.abs(d["contact"][idx]), 1.0))
+    _check_against_restatement(name, idx, jc)
+
+
+@pytest.mark.parametrize("name", SETS)
+def test_alpha_row_matches_reference_gradient(name):
+    """Row 3 of J is d alpha / d pose: within 5e-3 sc of the golden FD gradient where
+    alpha > 1e-2 (the bound test_gpu_implicit_matches_oracle uses for the implicit mode)."""
+    idx, (al, ct, jc, it, st) = _emulated(name)
+    d = _golden(name)
+    n = 0
+    for j, i in enumerate(idx):
+        if not d["alpha"][i] > 1e-2:
+            continue
+        J, _, _ = _restated(name, int(i))
+        sc = max(np.abs(J).max(), 1.0)
+        assert np.abs(jc[j, 3] - d["grad"][i]).max() <= 5e-3 * sc, (name, i)
+        n += 1
+    assert n >= 30
+
+
+def test_emulated_failure_rows_are_nan():
+    """A pair that does not converge gets NaN in all 48 entries (edge_cases at max_iter 3)."""
+    d, idx = _pairs("edge_cases", 12)
+    al, ct, jc, it, st = emul_jac(d, idx, max_iter=3)
+    assert np.all(st == 1) and np.all(it == 3)
+    assert np.all(np.isnan(jc)) and np.all(np.isnan(al))
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def test_header_exports_and_binding_agree():
+    """The new entry points and constants: declared in include/dcol.h, exported by the
+    library, bound by dcol_amd._lib with the header's argument counts; the emulator's entry."""
+    from dcol_amd import _lib
+    txt = _header()
+    lib = _lib.load()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
+    for f in ("dcol_plan_run_jac", "dcol_prox_jacobian_host"):
+        m = re.search(rf"\bint\s+{f}\s*\(([^)]*)\)", txt)
+        assert m, f
+        assert re.search(rf" T {f}\b", out), f
+        assert hasattr(lib, f)
+        assert len(_lib.SIGNATURES[f][1]) == len(m.group(1).split(",")), f
+    assert int(re.search(r"\bDCOL_JACOBIAN\s*=\s*(\d+)", txt).group(1)) == _lib.JACOBIAN == 64
+    assert int(re.search(r"\bDCOL_PLAN_JACOBIAN\s*=\s*(\d+)", txt).group(1)) == _lib.PLAN_JACOBIAN == 8
+    assert int(re.search(r"#define\s+DCOL_ABI_VERSION\s+(\d+)", txt).group(1)) == _lib.ABI_VERSION == 5
+    if not os.path.exists(EMUL_LIB):
+        subprocess.run(["make", "-C", EMUL_DIR, "-j8", "-s"], check=True)
+    assert hasattr(ctypes.CDLL(EMUL_LIB), "dcol_emul_jac_batch")
+    # argument checks that need no device: a NULL plan
+    assert lib.dcol_plan_run_jac(None, None, None, 1e-6, 50, _lib.JACOBIAN, None, None, None, None, None, None,
+                                 None) == _lib.ERR_ARG
+    assert b"dcol_plan_run_jac" in lib.dcol_last_error()
+
+
+def test_jac_variant_list():
+    """One JAC copy per shape, at the dense kernel's first listed lane count and one wave per
+    SIMD, and the committed dcol_variants.inc lists exactly those."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("variants", os.path.join(PKG, "csrc", "variants.py"))
+    V = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(V)
+    shapes = [(n, s, o) for (n, s), os_ in sorted(V.OMAX.items()) for o in os_]
+    jac = V.jac(shapes)
+    assert [(n, s, o) for n, s, o, _, _ in jac] == shapes
+    for n, s, o, lpp, wps in jac:
+        assert lpp == V.configs(n, s, o)[0][0] and wps == 1
+    inc = open(os.path.join(PKG, "csrc", "dcol_variants.inc")).read()
+    body = inc.split("#define DCOL_JAC_VARIANTS(X)")[1].split("#define")[0]
+    assert re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), 0\)", body) == [tuple(str(v) for v in r) for r in jac]
+
+
+# ---------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------
+_IDS = {}
+
+
+def _register(engine, d):
+    """engine shape ids of a golden table's pairs (registered once per engine and table)"""
+    from dcol_amd import spec_from_arrays
+    key = (id(engine), id(d))
+    if key not in _IDS:
+        _IDS[key] = (engine, d, np.array([engine.register(spec_from_arrays(d, k)) for k in range(len(d["type"]))],
+                                         dtype=np.int32))
+    ids = _IDS[key][2]
+    return ids[d["s1"]], ids[d["s2"]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SETS)
+def test_gpu_jacobian_matches_restatement(engine, name):
+    """48 pairs per set through Engine.solve_host(jacobian=True) against the restatement (the
+    rule of the module docstring); in the same run alpha, contact, iters and status meet the
+    parity tolerances against the golden values, and the FD gradient is still written."""
+    from conftest import grad_close
+    d, idx = _pairs(name, 48)
+    s1, s2 = _register(engine, d)
+    res = engine.solve_host(s1[idx], s2[idx], d["pose1"][idx], d["pose2"][idx], tol=float(d["tol"]), grad="fd",
+                            jacobian=True)
+    assert res.jac.shape == (48, 4, 12)
+    np.testing.assert_array_equal(res.status, d["status"][idx])
+    np.testing.assert_array_equal(res.iters, d["iters"][idx])
+    assert np.all(alpha_close(res.alpha, d["alpha"][idx]))
+    assert np.all(np.abs(res.contact - d["contact"][idx]) <= 1e-6 * np.maximum(np.abs(d["contact"][idx]), 1.0))
+    assert np.all(grad_close(res.grad, d["grad"][idx]))
+    _check_against_restatement(name, idx, res.jac)
+
+
+def _mixed_selection(n_mixed, n_large):
+    """Pairs of synthetic_mixed and large_polytopes as one table-independent list of
+    (set name, pair index)"""
+    out = []
+    for name, n in (("synthetic_mixed", n_mixed), ("large_polytopes", n_large)):
+        if n:
+            out += [(name, int(i)) for i in _pairs(name, n)[1]]
+    return out
+
+
+def _run_guarded(engine, sel):
+    """The pairs sel on the device through Plan.run(jacobian=True) into a [48, B] window of a
+    [144, B] buffer pre-filled with a sentinel -> (plan, outputs as numpy, the buffer)"""
+    import torch
+    s1, s2, p1, p2 = [], [], [], []
+    for name, i in sel:
+        d = _golden(name)
+        a, b = _register(engine, d)
+        s1.append(a[i]); s2.append(b[i]); p1.append(d["pose1"][i]); p2.append(d["pose2"][i])
+    B = len(sel)
+    plan = engine.plan(np.array(s1, np.int32), np.array(s2, np.int32), cache=False, jacobian=True)
+    dev = torch.device("cuda", engine.device)
+    from dcol_amd.engine import alloc_outputs
+    out = alloc_outputs(B, dev, True, True)
+    SENT = -12345.678
+    big = torch.full((144, B), SENT, dtype=torch.float64, device=dev)
+    out["jac"] = big[48:96]
+    assert out["jac"].is_contiguous()
+    t1 = torch.tensor(np.ascontiguousarray(np.array(p1).T), dtype=torch.float64, device=dev)
+    t2 = torch.tensor(np.ascontiguousarray(np.array(p2).T), dtype=torch.float64, device=dev)
+    plan.run(t1, t2, grad="fd", contact=True, out=out, jacobian=True)
+    torch.cuda.synchronize(dev)
+    host = big.cpu().numpy()
+    assert np.all(host[:48] == SENT) and np.all(host[96:] == SENT), "a store outside the pairs' 48 B doubles"
+    jac = host[48:96].reshape(4, 12, B).transpose(2, 0, 1)
+    return plan, {k: v.cpu().numpy() for k, v in out.items() if k != "jac"}, jac
+
+
+def _check_selection(sel, o, jac):
+    assert np.all(o["status"] == 0)
+    excused = {}
+    for j, (name, i) in enumerate(sel):
+        d = _golden(name)
+        assert o["iters"][j] == d["iters"][i]
+        assert alpha_close(o["alpha"][j], d["alpha"][i])
+        J, cond, tol = _restated(name, i)
+        sc = max(np.abs(J).max(), 1.0)
+        err = np.abs(jac[j] - J).max()
+        print(f"{name}[{i}]: err {err / sc:.2e} tol {tol / sc:.2e} cond(H) {cond:.1e}")
+        if err <= tol:
+            continue
+        assert cond > COND_MAX, (name, i, err / sc, tol / sc, cond)
+        excused.setdefault(name, []).append(i)
+    assert all(len(v) <= EXCUSED_MAX for v in excused.values()), excused   # the module docstring's rule
+
+
+@pytest.mark.gpu
+def test_gpu_one_pair(engine):
+    """B = 1, a many-faced pair: one group of 8 or 16 lanes in a partial wave; lanes q >= 2 of
+    the group must not store, and nothing lands outside the pair's 48 doubles."""
+    sel = _mixed_selection(0, 3)[1:2]
+    plan, o, jac = _run_guarded(engine, sel)
+    assert plan.launch_form == "buckets" and plan.jacobian
+    assert all(b["lpp"] >= 4 for b in plan.buckets() if b["kind"] == "solve")
+    _check_selection(sel, o, jac)
+
+
+@pytest.mark.gpu
+def test_gpu_65_pairs_mixed_buckets(engine):
+    """B = 65 over both sets' shapes: several dense-row buckets, each with a partial last wave;
+    no bucket is structured (flags 2 / 4), row-partitioned (oe) or fused."""
+    sel = _mixed_selection(40, 25)
+    assert len(sel) == 65
+    plan, o, jac = _run_guarded(engine, sel)
+    assert plan.launch_form == "buckets" and plan.num_buckets > 2
+    for b in plan.buckets():
+        if b["kind"] == "solve":
+            assert b["oe"] == 0 and not (b["flags"] & 6), b
+    _check_selection(sel, o, jac)
+
+
+@pytest.mark.gpu
+def test_gpu_partial_group_wave(engine):
+    """A bucket of 4 or more lanes per pair holding 3 pairs: not a multiple of the 64 / LPP
+    groups of a wave, so the last wave is partial and most of its lanes belong to no pair."""
+    cands = _mixed_selection(0, 24)
+    by_key = {}
+    for name, i in cands:
+        d = _golden(name)
+        a, b = _register(engine, d)
+        bk = engine.plan([a[i]], [b[i]], cache=False, jacobian=True).buckets()[0]
+        if bk["kind"] == "solve" and bk["lpp"] >= 4:
+            by_key.setdefault((bk["N"], bk["nsoc"], bk["omax"], bk["lpp"]), []).append((name, i))
+    sel = next(v[:3] for v in by_key.values() if len(v) >= 3)
+    plan, o, jac = _run_guarded(engine, sel)
+    (bk,) = [b for b in plan.buckets() if b["kind"] == "solve"]
+    assert bk["lpp"] >= 4 and bk["pairs"] == 3 and 3 % (64 // bk["lpp"]) != 0
+    _check_selection(sel, o, jac)
+
+
+@pytest.mark.gpu
+def test_gpu_failure_rows(engine):
+    """edge_cases.  At max_iter = 3 every solvable pair has status MAXITER (the unsupported
+    pairs keep UNSUPPORTED) and all 48 entries of every pair are NaN.  At the default settings
+    the pairs with a non-zero status have NaN rows and the others finite rows."""
+    d = _golden("edge_cases")
+    s1, s2 = _register(engine, d)
+    res = engine.solve_host(s1, s2, d["pose1"], d["pose2"], tol=float(d["tol"]), max_iter=3, grad=None, jacobian=True)
+    np.testing.assert_array_equal(res.status, np.where(d["status"] == 2, 2, 1))
+    assert np.all(np.isnan(res.jac))
+    res = engine.solve_host(s1, s2, d["pose1"], d["pose2"], tol=float(d["tol"]), grad=None, jacobian=True)
+    np.testing.assert_array_equal(res.status, d["status"])
+    bad = res.status != 0
+    assert bad.any() and np.all(np.isnan(res.jac[bad]))
+    assert np.all(np.isfinite(res.jac[~bad]))
+
+
+@pytest.mark.gpu
+def test_gpu_case4_pair(engine):
+    """A case-4 pair (capsule x polygon, N = 7) with case4=True, jacobian=True against the
+    restatement called with case4=True."""
+    from oracle import dcol_oracle as O
+    from test_case4 import CAPSULE, POLYGON, case4_table
+    tab = case4_table(np.random.default_rng(5))
+    k1 = int(np.flatnonzero(tab["type"] == CAPSULE)[0])
+    k2 = int(np.flatnonzero(tab["type"] == POLYGON)[0])
+    from dcol_amd import spec_from_arrays
+    ids = [engine.register(spec_from_arrays(tab, k)) for k in (k1, k2)]
+    p1 = np.array([[0.1, -0.2, 0.3, 0.2, -0.1, 0.3]])
+    p2 = np.array([[1.4, 0.9, -0.6, -0.3, 0.25, 0.1]])
+    res = engine.solve_host([ids[0]], [ids[1]], p1, p2, grad=None, case4=True, jacobian=True)
+    assert res.status[0] == 0
+    a, b = O.shape_from_table(tab, k1), O.shape_from_table(tab, k2)
+    al, _, x, s, z, it, dims = O.proximity(a, p1[0, :3], p1[0, 3:], b, p2[0, :3], p2[0, 3:], 1e-6, True)
+    assert x.size == 7 and res.iters[0] == it and alpha_close(res.alpha[0], al)
+    th = np.concatenate([p1[0], p2[0]])
+    J, cond = contact_jacobian(O, a, b, x, s, z, th, dims, True)
+    tol = tolerance(O, a, b, x, s, z, th, dims, J, True)
+    err = np.abs(res.jac[0] - J).max()
+    print(f"case 4: err {err:.2e} tol {tol:.2e} cond(H) {cond:.1e}")
+    assert cond <= COND_MAX and err <= tol
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["scene_quad", "scene_cone"])
+def test_gpu_dropin_equals_batch_bitwise(engine, name):
+    """proximity_jacobian on one pair equals the batch result bitwise (alpha, contact, J)."""
+    from dcol_amd import default_engine
+    from proximity.proximity_jacobian import proximity_jacobian
+    from test_dropin import objects_from_golden, pose_pair
+    d, idx = _pairs(name, 48)
+    i = int(idx[17])
+    eng = default_engine()
+    s1, s2 = _register(eng, d)
+    res = eng.solve_host(s1[idx], s2[idx], d["pose1"][idx], d["pose2"][idx], tol=float(d["tol"]), grad=None,
+                         jacobian=True)
+    a, b = pose_pair(objects_from_golden(d), d, i)
+    alpha, contact, J = proximity_jacobian(a, b, float(d["tol"]))
+    assert J.shape == (4, 12)
+    assert alpha.tobytes() == res.alpha[17].tobytes()
+    assert contact.tobytes() == res.contact[17].tobytes()
+    assert J.tobytes() == res.jac[17].tobytes()
+
+
+@pytest.mark.gpu
+def test_gpu_run_jac_argument_errors(engine):
+    """dcol_plan_run_jac: DCOL_ERR_ARG with a message for the flag on a plan made without
+    DCOL_PLAN_JACOBIAN and for a NULL jac; DCOL_PLAN_JACOBIAN | DCOL_PLAN_SUSPEND is refused;
+    without the flag the call is dcol_plan_run."""
+    import torch
+    from dcol_amd import _lib
+    from dcol_amd.engine import Plan, alloc_outputs
+    d, idx = _pairs("scene_quad", 8)
+    s1, s2 = _register(engine, d)
+    dev = torch.device("cuda", engine.device)
+    t1 = torch.tensor(np.ascontiguousarray(d["pose1"][idx].T), device=dev)
+    t2 = torch.tensor(np.ascontiguousarray(d["pose2"][idx].T), device=dev)
+    lib = _lib.load()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def run_jac(plan, out, flags, jac):
+        return lib.dcol_plan_run_jac(plan.handle, ptr(t1), ptr(t2), 1e-6, 50, flags, ptr(out["alpha"]),
+                                     ptr(out["contact"]), ptr(out["grad"]), jac, ptr(out["iters"]), ptr(out["status"]), st)
+    plain = engine.plan(s1[idx], s2[idx], cache=False)
+    out = alloc_outputs(8, dev, True, True, want_jac=True)
+    assert run_jac(plain, out, _lib.JACOBIAN | _lib.CONTACT, ptr(out["jac"])) == _lib.ERR_ARG
+    assert b"DCOL_PLAN_JACOBIAN" in lib.dcol_last_error()
+    jplan = engine.plan(s1[idx], s2[idx], cache=False, jacobian=True)
+    assert run_jac(jplan, out, _lib.JACOBIAN | _lib.CONTACT, None) == _lib.ERR_ARG
+    assert b"jac" in lib.dcol_last_error()
+    with pytest.raises(_lib.DcolLibraryError, match="DCOL_PLAN_SUSPEND"):
+        Plan(engine.table, s1[idx], s2[idx], suspend=True, jacobian=True)
+    # without the flag: dcol_plan_run (here on the Jacobian plan's dense-row buckets)
+    ref = plain.run(t1, t2, grad="fd")
+    assert run_jac(jplan, out, _lib.GRAD_FD | _lib.CONTACT, None) == _lib.SUCCESS
+    torch.cuda.synchronize(dev)
+    np.testing.assert_array_equal(out["status"].cpu().numpy(), ref["status"].cpu().numpy())
+    np.testing.assert_array_equal(out["iters"].cpu().numpy(), ref["iters"].cpu().numpy())
+    assert np.all(alpha_close(out["alpha"].cpu().numpy(), ref["alpha"].cpu().numpy()))

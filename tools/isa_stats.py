@@ -9,7 +9,10 @@ allocator parked in AGPRs), DPP lane moves, selects, scratch traffic -- plus the
 register / scratch totals.  Used for the row-partition work.
 Usage: python3 tools/isa_stats.py N:NSOC:OMAX:LPP[:OE[:FL]] [--waves 1] ...
   FL bits: 1 FULL, 2 BALL, 4 CONE, 8 BOX, 64 FD-only (as variants.py), 32 LDS rows (Solver GLDS; WPS >= 10
-  in variants.py), 256 split ball SOC block (Solver SPLIT; variants.py FL bit 32)
+  in variants.py), 256 split ball SOC block (Solver SPLIT; variants.py FL bit 32), 512 the
+  contact-point Jacobian copy (solve_one JAC; also reports "loops": (instructions, scratch
+  instructions) of every outermost loop in program order -- the PDIP iteration first, the
+  Jacobian's four output rows last)
 """
 import argparse
 import os
@@ -27,7 +30,7 @@ __global__ void __launch_bounds__(64, {w}) kb(KArgs A) {{
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t slot = t / {l}; const int q = (int)(t % {l});
     if (slot >= A.n) return;
-    solve_one<{n}, {s}, {o}, {l}, {full}, {ball}, {cone}, {oe}, 0, {glds}, {box}, {fdonly}, {split}>(A, slot, q);
+    solve_one<{n}, {s}, {o}, {l}, {full}, {ball}, {cone}, {oe}, 0, {glds}, {box}, {fdonly}, {split}, {jac}>(A, slot, q);
 }}
 }}
 """
@@ -51,7 +54,8 @@ def stats(spec, waves, extra=()):
         open(src, "w").write(SRC.format(n=n, s=s, o=o, l=l, oe=oe, w=waves, full="true" if fl & 1 else "false",
                                         ball="true" if fl & 2 else "false", cone="true" if fl & 4 else "false",
                                         glds="true" if fl & 32 else "false", box="true" if fl & 8 else "false",
-                                        fdonly="true" if fl & 64 else "false", split="true" if fl & 256 else "false"))
+                                        fdonly="true" if fl & 64 else "false", split="true" if fl & 256 else "false",
+                                        jac="true" if fl & 512 else "false"))
         r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", f"-I{CSRC}",
                             *extra, "-S", "--offload-device-only", src, "-o", asm], capture_output=True, text=True)
         if r.returncode:
@@ -93,9 +97,12 @@ def stats(spec, waves, extra=()):
         if "dpp" in t or "quad_perm" in t or "row_" in t:
             dpp += 1
     total = len(loop)
-    return {"kernel": spec, "waves": waves, "loop_instructions": total, **cnt, "dpp": dpp,
-            "agpr_frac": round(cnt["agpr_move"] / max(total, 1), 3), "fp64_frac": round(cnt["fp64"] / max(total, 1), 3),
-            "kernel_instructions": len(ins), **meta}
+    out = {"kernel": spec, "waves": waves, "loop_instructions": total, **cnt, "dpp": dpp,
+           "agpr_frac": round(cnt["agpr_move"] / max(total, 1), 3), "fp64_frac": round(cnt["fp64"] / max(total, 1), 3),
+           "kernel_instructions": len(ins), **meta}
+    if fl & 512:
+        out["loops"] = [(len(v), sum(1 for t in v if CATS[3][1].match(t.split()[0]))) for v in loops.values()]
+    return out
 
 
 def main():
