@@ -329,7 +329,9 @@ const char* dcol_status_string(int32_t s) {
         case DCOL_UNSUPPORTED: return "Failed to combine problem matrices.";
         case DCOL_NOT_PD: return "Matrix is not positive definite";
         case DCOL_NONFINITE: return "array must not contain infs or NaNs";
-        case DCOL_TOO_LARGE: return "pair exceeds the engine's orthant-row capacity";
+        case DCOL_TOO_LARGE:
+            return "pair exceeds the engine's orthant-row capacity (1024 rows; 32 for a case-4 pair, 128 with the "
+                   "contact-point Jacobian)";
         default: return "unknown status";
     }
 }
@@ -547,7 +549,8 @@ int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const
     if (e == hipSuccess) e = hipMalloc(&p->d_s2, sizeof(int32_t) * B);
     if (e == hipSuccess) e = hipMemcpy(p->d_s1, s1, sizeof(int32_t) * B, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->d_s2, s2, sizeof(int32_t) * B, hipMemcpyHostToDevice);
-    if (e == hipSuccess && p->launches.size() > 1) {
+    // (a lone streamed bucket too: its slots are sorted by row count)
+    if (e == hipSuccess && (p->launches.size() > 1 || (p->launches[0].stream && B > 1))) {
         e = hipMalloc(&p->d_perm, sizeof(int32_t) * B);
         if (e == hipSuccess) e = hipMemcpy(p->d_perm, p->lay.perm.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice);
     }
@@ -790,6 +793,8 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
             if (e == hipSuccess) e = launch_susp(L.N, L.nsoc, L.omax, L.lpp, L.flags(), L.oe, b, ls);
         } else if (want_jac) {   // (a Jacobian plan: dense rows, no hint)
             e = launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls);
+        } else if (L.stream) {   // a wave per pair: nothing to regroup, so no hint
+            e = launch_stream(L.N, L.nsoc, a, ls);
         } else {
             const int split = (L.oe > 0 && L.lpp == 2 && split_enabled() && split_built(L.N, L.nsoc, L.omax, L.oe))
                                   ? LF_SPLIT : 0;

@@ -2974,4 +2974,745 @@ __global__ void __launch_bounds__(kSolveBlock, WPS % 10) prox_resume_kernel(KArg
     solve_one<N, NSOC, OMAX, LPP, (FL & 1) != 0, (FL & 2) != 0, (FL & 4) != 0, OE, 2, false, (FL & 8) != 0>(A, pi, q, ci);
 }
 
+// ------------------------------------------------------------------------------------
+// the streamed-row solver: pairs above the register kernels' 128 orthant rows
+// ------------------------------------------------------------------------------------
+// One WAVE owns one pair.  Orthant row i lives in lane i % LANES, slot i / LANES, and the
+// slots are walked by a run-time loop over ceil(o / LANES) of them, so the row count is a
+// run-time value up to kStreamMaxRows.  Nothing per row sits in registers:
+//  * the row state -- s, z, the carried residual r = G x - h and two per-iteration
+//    temporaries -- lives in LDS, laid out [field][slot][lane] (a wave's access to a slot of
+//    a field is 64 consecutive doubles);
+//  * the G row is not stored at all: every orthant row of every primitive is
+//    [Qe a, g3, ex0, ex1] with h = (Qe a).re (DevRow, digest_shape), so each pass over the
+//    rows re-forms it from the 64-byte descriptor in the row pool (shared by every pair of
+//    the shape, resident in L1 / L2) and the pair's two frames.
+// Sums over rows (G'DG, G'v, s'z, the ratio tests' maxima) are wave all-reduces (Grp<64>)
+// that leave bitwise the same value in every lane; the SOC blocks (at most two, dense rows)
+// and the N x N part -- factorisation, solves, mu, sigma, step lengths -- are then
+// replicated in every lane and every branch of the iteration is wave-uniform.  The SOC
+// blocks' share is added after the reduction, once.
+//
+// Same algorithm and row arithmetic as Solver's dense-row path (the formulas of pdip(),
+// rhs_solve(), orth_step(), predictor() above, quirks Q1-Q13 included); against it only the
+// order of the row sums differs (rounding level).  The iteration makes four passes that
+// need G (normal matrix + predictor right-hand side, predictor step, corrector right-hand
+// side, corrector step) and one LDS-only pass (the update, which also takes s'z of the next
+// iteration).  LANES = 1: the x86 build (tests/emul_stream) -- one lane walks every row and
+// the reductions are the identity.
+constexpr int kStreamMaxRows = 1024;   // include/dcol.h DCOL_MAX_PAIR_ROWS
+constexpr int kStreamFields = 5;       // doubles of LDS row state per orthant row
+constexpr int kStreamLdsDoubles = kStreamFields * kStreamMaxRows;   // 40 KiB per workgroup
+// the built instances (N, NSOC): the combine cases 1-3 in which a polytope or a polygon can
+// bring many rows (dcol_kernels_stream.hip; dcol_host.hpp classify routes only these)
+#define DCOL_STREAM_SHAPES(X) X(4, 0) X(4, 1) X(5, 1) X(6, 1) X(6, 2)
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ double readlane_d(double v, int l) {
+    const long long b = __double_as_longlong(v);
+    int lo = (int)(b & 0xffffffffLL), hi = (int)(b >> 32);
+    lo = __builtin_amdgcn_readlane(lo, l);
+    hi = __builtin_amdgcn_readlane(hi, l);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+#define DCOL_RDL(v, l) readlane_d(v, l)
+#else
+#define DCOL_RDL(v, l) (__builtin_trap(), (v))   // whole-wave groups run on the GPU only
+#endif
+// the whole wave: the 16-lane butterflies leave each DPP row's value in all of its lanes;
+// the four rows' values are read as wave-uniform scalars and combined in one fixed order
+template <>
+struct Grp<64> {
+    DCOL_HD static double sum(double v) {
+        v = Grp<16>::sum(v);
+        return (DCOL_RDL(v, 0) + DCOL_RDL(v, 16)) + (DCOL_RDL(v, 32) + DCOL_RDL(v, 48));
+    }
+    DCOL_HD static double min(double v) {
+        v = Grp<16>::min(v);
+        return fmin(fmin(DCOL_RDL(v, 0), DCOL_RDL(v, 16)), fmin(DCOL_RDL(v, 32), DCOL_RDL(v, 48)));
+    }
+    DCOL_HD static double max(double v) {
+        v = Grp<16>::max(v);
+        return fmax(fmax(DCOL_RDL(v, 0), DCOL_RDL(v, 16)), fmax(DCOL_RDL(v, 32), DCOL_RDL(v, 48)));
+    }
+};
+
+template <int N, int NSOC, int LANES>
+struct StreamSolver {
+    static_assert(LANES == 64 || LANES == 1, "a whole wave per pair, or the one-lane x86 build");
+    static_assert(kStreamMaxRows % LANES == 0, "whole slots");
+    using R = Grp<LANES>;
+    // the N x N helpers (chol, chol_solve, q1_solve), the dense SOC rows (soc_rows) and the
+    // per-primitive gradient formulas are Solver's own; no row of this instance is used
+    using FS = Solver<N, NSOC, 1, 1>;
+    using Agg = typename FS::LagAgg;
+    static constexpr int SSA = NSOC > 0 ? NSOC : 1;
+    static constexpr int SLOTS = kStreamMaxRows / LANES;   // slot capacity
+    enum : int { FS_ = 0, FZ_ = 1, FR_ = 2, FC_ = 3, FU_ = 4 };   // LDS fields: s, z, r, c (cp, then dz), u = G dx
+#if defined(__HIP_DEVICE_COMPILE__)
+    using lds_d = __attribute__((address_space(3))) double;
+#else
+    using lds_d = double;
+#endif
+    lds_d* ws;                 // this lane's first element of the row state
+    const double* __restrict__ rows;
+    int lane, o1, o, nslot, ro1, ro2;
+    double Qe1[9], re1[3], Qe2[9], re2[3];
+    // SOC blocks (dense rows, every lane the same values); rs holds h until initialize()
+    double Gs[SSA][4][N], ss[SSA][4], zs[SSA][4], rs[SSA][4];
+    int soc_owner[SSA], soc_kind[SSA];
+    double x[N], vimp[N];
+    double sz;                 // s'z of the current iterate (initialize(), then the update pass)
+
+    DCOL_HD lds_d& fld(int f, int k) const { return ws[(f * SLOTS + k) * LANES]; }
+
+    // orthant row i of the pair: G row into g, h into h
+    DCOL_HD void row(int i, double (&g)[N], double& h) const {
+        const bool p2 = i >= o1;
+        const int ri = p2 ? ro2 + (i - o1) : ro1 + i;
+        const double2* rw = reinterpret_cast<const double2*>(rows + 8 * (int64_t)ri);
+        const double2 q0 = rw[0], q1 = rw[1], q2 = rw[2];
+        const double a0 = q0.x, a1 = q0.y, a2 = q1.x;
+        double Q[9], re[3];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Q[c] = p2 ? Qe2[c] : Qe1[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) re[c] = p2 ? re2[c] : re1[c];
+        g[0] = Q[0] * a0 + Q[1] * a1 + Q[2] * a2;
+        g[1] = Q[3] * a0 + Q[4] * a1 + Q[5] * a2;
+        g[2] = Q[6] * a0 + Q[7] * a1 + Q[8] * a2;
+        g[3] = q1.y;
+        // cases 1-3: the one primitive with extra columns puts them at columns 4, 5; the
+        // other's descriptors carry zeros there
+        if constexpr (N > 4) g[4] = q2.x;
+        if constexpr (N > 5) g[5] = q2.y;
+        h = g[0] * re[0] + g[1] * re[1] + g[2] * re[2];
+    }
+    DCOL_HD static double dotn(const double* g, const double* v) {
+        double acc = g[0] * v[0];
+#pragma unroll
+        for (int j = 1; j < N; ++j) acc += g[j] * v[j];
+        return acc;
+    }
+    DCOL_HD static void allsum_sym(double (&H)[N][N]) {
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = j; c < N; ++c) H[j][c] = R::sum(H[j][c]);
+    }
+    DCOL_HD static void allsum_vec(double* v) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) v[j] = R::sum(v[j]);
+    }
+
+    DCOL_HD void assemble(const KArgs& A, const DevShape& S1, const DevShape& S2, const Frame& F1, const Frame& F2) {
+        rows = reinterpret_cast<const double*>(A.rows);
+        o1 = S1.n_ort;
+        o = o1 + S2.n_ort;
+        nslot = (o + LANES - 1) / LANES;
+        ro1 = S1.row_off;
+        ro2 = S2.row_off;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            Qe1[c] = F1.Qe[c];
+            Qe2[c] = F2.Qe[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            re1[c] = F1.re[c];
+            re2[c] = F2.re[c];
+        }
+        // SOC block 0 = first primitive with a SOC, block 1 = prim 2 when both have one
+        const int own0 = S1.soc_kind != SOC_NONE ? 0 : 1;
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            const bool p2 = (b == 0) ? (own0 == 1) : true;
+            soc_owner[b] = p2 ? 1 : 0;
+            soc_kind[b] = p2 ? S2.soc_kind : S1.soc_kind;
+            double Q[9], re[3];   // element-wise select of the block's frame
+#pragma unroll
+            for (int c = 0; c < 9; ++c) Q[c] = p2 ? Qe2[c] : Qe1[c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) re[c] = p2 ? re2[c] : re1[c];
+            FS::soc_rows(soc_kind[b], p2 ? S2.R : S1.R, p2 ? S2.cone_c : S1.cone_c, p2 ? S2.tanb : S1.tanb,
+                         p2 ? S2.n_extra : S1.n_extra, 0, Q, re, Gs[b], rs[b]);
+        }
+    }
+
+    // bring2cone's shift (pdip.py:237-287, quirk Q11) from the orthant rows' wave-reduced
+    // (any <= 0, minimum) and the SOC blocks' values v: the shift 1 + a, or a negative value
+    // for "already inside"
+    DCOL_HD static double cone_shift(double any, double mn, const double (*v)[4]) {
+        double socv = -__builtin_inf();
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            const double res = v[b][0] - sqrt(tail_dot<4>(v[b], v[b]));
+            socv = (res <= 0.0) ? fmax(socv, -res) : socv;
+        }
+        double a = -1.0;
+        if (any > 0.0) a = -mn;
+        a = fmax(a, socv);
+        return a >= 0.0 ? 1.0 + a : -1.0;
+    }
+
+    // -------- initialize, pdip.py:291-332 ------------------------------------------------
+    DCOL_HD bool initialize() {
+        double H[N][N], F[N][N], idg[N], gth[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            gth[j] = 0.0;
+#pragma unroll
+            for (int c = j; c < N; ++c) H[j][c] = 0.0;
+        }
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double g[N], h;
+                row(i, g, h);
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    gth[j] += g[j] * h;
+#pragma unroll
+                    for (int c = j; c < N; ++c) H[j][c] += g[j] * g[c];
+                }
+            }
+        }
+        allsum_sym(H);
+        allsum_vec(gth);
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    gth[j] += Gs[b][e][j] * rs[b][e];   // rs holds h here
+#pragma unroll
+                    for (int c = j; c < N; ++c) H[j][c] += Gs[b][e][j] * Gs[b][e][c];
+                }
+        const bool ok = FS::chol(H, F, idg);         // F' = np.linalg.cholesky(G'G)
+        FS::chol_solve(F, idg, gth, x);              // x_hat = L^-T L^-1 G'h
+        double xz[N];
+        FS::q1_solve(F, idg, xz);                    // quirk Q1
+        // r = G x_hat - h (quirk Q2: s~ = G x_hat - h), z~ = G xz; the cones' shifts need the
+        // whole pair's minima first, so the rows are stored unshifted and shifted below
+        double anys = 0.0, mns = __builtin_inf(), anyz = 0.0, mnz = __builtin_inf();
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double g[N], h;
+                row(i, g, h);
+                const double rk = dotn(g, x) - h;
+                const double zk = dotn(g, xz);
+                fld(FR_, k) = rk;
+                fld(FS_, k) = rk;
+                fld(FZ_, k) = zk;
+                anys = (rk <= 0.0) ? 1.0 : anys;
+                mns = fmin(mns, rk);
+                anyz = (zk <= 0.0) ? 1.0 : anyz;
+                mnz = fmin(mnz, zk);
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                rs[b][e] = dotn(Gs[b][e], x) - rs[b][e];
+                ss[b][e] = rs[b][e];
+                zs[b][e] = dotn(Gs[b][e], xz);
+            }
+        const double shs = cone_shift(R::max(anys), R::min(mns), ss);
+        const double shz = cone_shift(R::max(anyz), R::min(mnz), zs);
+        double szl = 0.0;
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double sk = fld(FS_, k), zk = fld(FZ_, k);
+                if (shs >= 0.0) sk = sk + shs;
+                if (shz >= 0.0) zk = zk + shz;
+                fld(FS_, k) = sk;
+                fld(FZ_, k) = zk;
+                szl = fma(sk, zk, szl);
+            }
+        }
+        sz = R::sum(szl);
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            if (shs >= 0.0) ss[b][0] = ss[b][0] + shs;
+            if (shz >= 0.0) zs[b][0] = zs[b][0] + shz;
+            sz = sz + full_dot<4>(ss[b], zs[b]);
+        }
+        return ok;
+    }
+
+    struct SocState {
+        SocNT W;
+        double lam[4], ll[4];
+    };
+    // Hm += G_b' W^-2 G_b through G~_b = W^-1 G_b (Solver::soc_hadd, dense rows)
+    DCOL_HD void soc_hadd(int b, const SocNT& W, double (&Hm)[N][N]) const {
+        double gt[4][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            double col[4], res[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) col[e] = Gs[b][e][j];
+            soc_solve(W, col, res);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) gt[e][j] = res[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+#pragma unroll
+                for (int c = j; c < N; ++c) Hm[j][c] += gt[e][j] * gt[e][c];
+    }
+    DCOL_HD void soc_gtv(int b, const double* v, double* out) const {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int j = 0; j < N; ++j) out[j] += Gs[b][e][j] * v[e];
+    }
+    // the SOC blocks' share of a right-hand side and its solve (Solver::rhs_solve): predictor
+    // (cp == nullptr) or corrector; rhs holds the orthant rows' wave sum
+    DCOL_HD void soc_rhs_solve(const SocState* so, const double (&F)[N][N], const double (&idg)[N],
+                               const double (*cp)[4], double smu, double* rhs, double* dx, double (*sbzt)[4]) const {
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            double sr[4], q[4], bz[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sr[e] = ss[b][e] + rs[b][e];
+            soc_w2inv(so[b].W, sr, q);
+            if (!cp) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    sbzt[b][e] = zs[b][e] - q[e];
+                    bz[e] = -q[e];
+                }
+            } else {
+                double v[4], lds[4], m[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = -so[b].ll[e] - cp[b][e];
+                v[0] += smu;                     // + smu e (the head coordinate)
+                soc_iprod(so[b].lam, v, lds);
+                soc_solve(so[b].W, lds, m);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sbzt[b][e] = -q[e] - m[e];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bz[e] = sbzt[b][e] - zs[b][e];
+            }
+            soc_gtv(b, bz, rhs);
+        }
+        rhs[3] -= 1.0;                           // - c (c = e_3)
+        FS::chol_solve(F, idg, rhs, dx);
+    }
+    // one SOC block of a step (Solver::soc_step) and its share of the step bound
+    DCOL_HD double soc_step(int b, const SocNT& W, const double* wbz, const double* dx, double* u, double* dz, double* ds,
+                            double cmax) const {
+        double t[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[e] = dotn(Gs[b][e], dx);
+        soc_w2inv(W, u, t);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            dz[e] = t[e] - wbz[e];
+            ds[e] = -(ss[b][e] + rs[b][e]) - u[e];
+        }
+        const double ib = fmax(soc_ls_inv(ss[b], ds, W.lis[0], W.lrc[0]), soc_ls_inv(zs[b], dz, W.lis[1], W.lrc[1]));
+        return fmax(cmax, ib);
+    }
+
+    // -------- solve_lp_pdip, pdip.py:373-470 -------------------------------------------
+    DCOL_HD int32_t pdip(double tol, int max_iter, int* it_out) {
+        int it = 0;
+        int32_t st = ST_MAXITER;
+        const double degd = (double)(o + NSOC);          // quirk Q7
+        const double rdeg = 1.0 / degd;
+        for (it = 0; it < max_iter; ++it) {
+            // ---- mu = s'z / deg and the exit test first (pdip.py:410-422, quirk Q3)
+            const double mq = sz * rdeg;
+            const double mu = fma(fma(-mq, degd, sz), rdeg, mq);
+            if (mu < tol) {
+                st = ST_OK;
+                break;
+            }
+            // ---- pass A: normal matrix G'W^-2 G and the predictor's right-hand side
+            double Hm[N][N], rhs[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                rhs[j] = 0.0;
+#pragma unroll
+                for (int c = j; c < N; ++c) Hm[j][c] = 0.0;
+            }
+            for (int k = 0; k < nslot; ++k) {
+                const int i = k * LANES + lane;
+                if (i < o) {
+                    double g[N], h;
+                    row(i, g, h);
+                    const double sk = fld(FS_, k), zk = fld(FZ_, k), rk = fld(FR_, k);
+                    const double d = zk * (zk * frcp1(sk * zk));   // W^-2 = z / s on the orthant
+                    const double t = -(d * (sk + rk));
+                    double gd[N];
+#pragma unroll
+                    for (int j = 0; j < N; ++j) gd[j] = g[j] * d;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) {
+                        rhs[j] += g[j] * t;
+#pragma unroll
+                        for (int c = j; c < N; ++c) Hm[j][c] += gd[j] * g[c];
+                    }
+                }
+            }
+            allsum_sym(Hm);
+            allsum_vec(rhs);
+            SocState so[SSA];
+#pragma unroll
+            for (int b = 0; b < NSOC; ++b) {
+                soc_nt(ss[b], zs[b], so[b].W);
+                soc_mul(so[b].W, zs[b], so[b].lam);
+                soc_prod(so[b].lam, so[b].lam, so[b].ll);
+                soc_hadd(b, so[b].W, Hm);
+            }
+            double F[N][N], idg[N];
+            if (!FS::chol(Hm, F, idg)) {                    // scipy check_finite -> ValueError,
+                bool finite = true;                         // else LinAlgError (not PD)
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+#pragma unroll
+                    for (int c = j; c < N; ++c) finite = finite && __builtin_isfinite(Hm[j][c]);
+                st = finite ? ST_NOT_PD : ST_NONFINITE;
+                break;
+            }
+            // ---- predictor (affine) direction
+            double dx[N], sbzt[SSA][4];
+            soc_rhs_solve(so, F, idg, nullptr, 0.0, rhs, dx, sbzt);
+            // ---- pass B: the predictor step's cross term cp = ds o dz, bound and the sums
+            // p1 = s'dz + z'ds, p2 = ds'dz (Solver::predictor)
+            double cmax = 1.0, p1 = 0.0, p2 = 0.0;
+            for (int k = 0; k < nslot; ++k) {
+                const int i = k * LANES + lane;
+                if (i < o) {
+                    double g[N], h;
+                    row(i, g, h);
+                    const double sk = fld(FS_, k), zk = fld(FZ_, k), rk = fld(FR_, k);
+                    const double is = zk * frcp1(sk * zk);
+                    const double u = dotn(g, dx);
+                    const double t = (u + rk) * is;
+                    const double dz = zk * t;
+                    const double ds = -(sk + rk) - u;
+                    cmax = fmax(cmax, -ds * is);
+                    cmax = fmax(cmax, -t);
+                    const double c = ds * dz;
+                    fld(FC_, k) = c;
+                    p1 = fma(sk, dz, fma(zk, ds, p1));
+                    p2 = p2 + c;
+                }
+            }
+            cmax = R::max(cmax);
+            p1 = R::sum(p1);
+            p2 = R::sum(p2);
+            double cpS[SSA][4];
+#pragma unroll
+            for (int b = 0; b < NSOC; ++b) {
+                double u[4], dz[4], ds[4], t1[4], t2[4];
+                cmax = soc_step(b, so[b].W, sbzt[b], dx, u, dz, ds, cmax);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    p1 = fma(ss[b][e], dz[e], fma(zs[b][e], ds[e], p1));
+                    p2 = fma(ds[e], dz[e], p2);
+                }
+                soc_solve(so[b].W, ds, t1);
+                soc_mul(so[b].W, dz, t2);
+                soc_prod(t1, t2, cpS[b]);
+            }
+            const double aa = frcp1(cmax);                          // quirk Q5 (no 0.99)
+            const double rho = (sz + fma(aa, p1, (aa * aa) * p2)) * frcp1(sz);
+            const double sc = fmax(0.0, fmin(1.0, rho));
+            const double sigma = sc * sc * sc;                      // quirk Q6
+            const double smu = sigma * mu;
+            // ---- pass C: the corrector's right-hand side
+#pragma unroll
+            for (int j = 0; j < N; ++j) rhs[j] = 0.0;
+            for (int k = 0; k < nslot; ++k) {
+                const int i = k * LANES + lane;
+                if (i < o) {
+                    double g[N], h;
+                    row(i, g, h);
+                    const double sk = fld(FS_, k), zk = fld(FZ_, k), rk = fld(FR_, k);
+                    const double is = zk * frcp1(sk * zk);
+                    const double num = fma(zk, sk + rk, smu - fld(FC_, k));
+                    const double t = -num * is;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) rhs[j] += g[j] * t;
+                }
+            }
+            allsum_vec(rhs);
+            soc_rhs_solve(so, F, idg, cpS, smu, rhs, dx, sbzt);
+            // ---- pass D: the corrector step (Solver::orth_step); u = G dx and dz stay in LDS
+            // for the update
+            cmax = 1.0;
+            for (int k = 0; k < nslot; ++k) {
+                const int i = k * LANES + lane;
+                if (i < o) {
+                    double g[N], h;
+                    row(i, g, h);
+                    const double sk = fld(FS_, k), zk = fld(FZ_, k), rk = fld(FR_, k);
+                    const double rsz = frcp1(sk * zk);
+                    const double is = zk * rsz;
+                    const double u = dotn(g, dx);
+                    const double num = fma(zk, u + rk, smu - fld(FC_, k));
+                    const double ds = -(sk + rk) - u;
+                    cmax = fmax(cmax, -ds * is);
+                    cmax = fmax(cmax, -num * rsz);   // -dz / z = -num / (s z)
+                    fld(FU_, k) = u;
+                    fld(FC_, k) = num * is;          // dz
+                }
+            }
+            cmax = R::max(cmax);
+            double su[SSA][4], sdz[SSA][4], sds[SSA][4];
+#pragma unroll
+            for (int b = 0; b < NSOC; ++b) cmax = soc_step(b, so[b].W, sbzt[b], dx, su[b], sdz[b], sds[b], cmax);
+            const double a = fmin(1.0, 0.99 * frcp1(cmax));
+            // ---- update, and s'z of the new iterate
+#pragma unroll
+            for (int j = 0; j < N; ++j) x[j] += a * dx[j];
+            double szl = 0.0;
+            for (int k = 0; k < nslot; ++k) {
+                const int i = k * LANES + lane;
+                if (i < o) {
+                    double sk = fld(FS_, k), zk = fld(FZ_, k), rk = fld(FR_, k);
+                    const double u = fld(FU_, k);
+                    const double ds = -(sk + rk) - u;
+                    rk += a * u;
+                    sk += a * ds;
+                    zk += a * fld(FC_, k);
+                    fld(FR_, k) = rk;
+                    fld(FS_, k) = sk;
+                    fld(FZ_, k) = zk;
+                    szl = fma(sk, zk, szl);
+                }
+            }
+            sz = R::sum(szl);
+#pragma unroll
+            for (int b = 0; b < NSOC; ++b) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    rs[b][e] += a * su[b][e];
+                    ss[b][e] += a * sds[b][e];
+                    zs[b][e] += a * sdz[b][e];
+                }
+                sz = sz + full_dot<4>(ss[b], zs[b]);
+            }
+        }
+        *it_out = it;
+        return st;
+    }
+
+    // -------- gradient -------------------------------------------------------------------
+    // The implicit mode's v = H^-1 e3 at the returned iterate (Solver::implicit_weights);
+    // false if the normal matrix does not factor there
+    DCOL_HD bool implicit_v(SocNT* W) {
+        double Hm[N][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = j; c < N; ++c) Hm[j][c] = 0.0;
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double g[N], h;
+                row(i, g, h);
+                const double sk = fld(FS_, k), zk = fld(FZ_, k);
+                const double d = zk * (zk * frcp1(sk * zk));
+                double gd[N];
+#pragma unroll
+                for (int j = 0; j < N; ++j) gd[j] = g[j] * d;
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+#pragma unroll
+                    for (int c = j; c < N; ++c) Hm[j][c] += gd[j] * g[c];
+            }
+        }
+        allsum_sym(Hm);
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            soc_nt(ss[b], zs[b], W[b]);
+            soc_hadd(b, W[b], Hm);
+        }
+        double F[N][N], idg[N], e3[N];
+        const bool fine = FS::chol(Hm, F, idg);
+#pragma unroll
+        for (int j = 0; j < N; ++j) e3[j] = (j == 3) ? 1.0 : 0.0;
+        FS::chol_solve(F, idg, e3, vimp);
+        return fine;
+    }
+    // The two primitives' aggregates (Solver::lag_aggregate) in one pass over the rows: with
+    // the duals z as weights (agZ) and, imp: also with the implicit mode's a = -W^-2 G v
+    // (agA; W: implicit_v's scalings)
+    DCOL_HD void aggregates(const DevShape& S1, const DevShape& S2, bool imp, const SocNT* W, Agg (&agZ)[2],
+                            Agg (&agA)[2]) const {
+        double uz[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, ua[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double g[N], h;
+                row(i, g, h);
+                const bool p2 = i >= o1;
+                const double sk = fld(FS_, k), zk = fld(FZ_, k);
+                const double wa = imp ? -((zk * (zk * frcp1(sk * zk))) * dotn(g, vimp)) : 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    uz[0][c] = fma(p2 ? 0.0 : zk, g[c], uz[0][c]);
+                    uz[1][c] = fma(p2 ? zk : 0.0, g[c], uz[1][c]);
+                    ua[0][c] = fma(p2 ? 0.0 : wa, g[c], ua[0][c]);
+                    ua[1][c] = fma(p2 ? wa : 0.0, g[c], ua[1][c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int kind = NSOC > 0 ? (p ? S2.soc_kind : S1.soc_kind) : SOC_NONE;
+            agZ[p].kind = agA[p].kind = kind;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                agZ[p].u[c] = R::sum(uz[p][c]);
+                agA[p].u[c] = imp ? R::sum(ua[p][c]) : 0.0;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) agZ[p].zs[e] = agA[p].zs[e] = 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b) {
+            double wa[4] = {0.0, 0.0, 0.0, 0.0};
+            if (imp) {
+                double u[4], t[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[e] = dotn(Gs[b][e], vimp);
+                soc_w2inv(W[b], u, t);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) wa[e] = -t[e];
+            }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                if (soc_owner[b] != p) continue;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    agZ[p].zs[e] = zs[b][e];
+                    agA[p].zs[e] = wa[e];
+                    if (soc_kind[b] == SOC_CONE) {   // cone rows: Qe(-E e_k)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            agZ[p].u[c] = fma(zs[b][e], Gs[b][e][c], agZ[p].u[c]);
+                            agA[p].u[c] = fma(wa[e], Gs[b][e][c], agA[p].u[c]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// One pair by the streamed-row solver; every lane of the wave calls it (lane = 0 in the
+// one-lane build).  ws: the pair's row state, kStreamLdsDoubles doubles (the workgroup's
+// LDS).  Writes what solve_one writes, from lane 0.
+template <int N, int NSOC, int LANES>
+DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamSolver<N, NSOC, LANES>::lds_d* ws) {
+    using Slv = StreamSolver<N, NSOC, LANES>;
+    const int64_t B = A.B;
+    const int k1 = A.s1[pi], k2 = A.s2[pi];
+    const DevShape& S1 = A.shapes[k1];
+    const DevShape& S2 = A.shapes[k2];
+    double th1[6], th2[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        th1[c] = A.pose1[c * B + pi];
+        th2[c] = A.pose2[c * B + pi];
+    }
+    Frame F1, F2;
+    make_frame(S1, th1, F1);
+    make_frame(S2, th2, F2);
+    Slv P;
+    P.lane = lane;
+    P.ws = ws + lane;
+    int it = 0;
+    int32_t st;
+    // (the host never routes such a pair here -- classify(); the row state has no room for it)
+    if (S1.n_ort + S2.n_ort > kStreamMaxRows) {
+        st = ST_TOO_LARGE;
+    } else {
+        P.assemble(A, S1, S2, F1, F2);
+        st = !P.initialize() ? ST_NOT_PD : P.pdip(A.tol, A.max_iter, &it);
+    }
+    const double nan = __builtin_nan("");
+    const bool ok = st == ST_OK;
+    double g[12];
+    const bool want_grad = (A.flags & (F_GRAD_FD | F_GRAD_ENV | F_GRAD_IMP)) && (A.grad || A.rec);
+    if (want_grad) {
+        if (ok) {
+            using Agg = typename Slv::Agg;
+            const bool imp = (A.flags & F_GRAD_IMP) != 0;
+            SocNT W[Slv::SSA];
+            const bool imp_ok = imp && P.implicit_v(W);
+            Agg agZ[2], agA[2];
+            P.aggregates(S1, S2, imp, W, agZ, agA);
+            typename Slv::FS Fm;   // the formulas read x, vimp and the (zero) column offset only
+            Fm.q = 0;
+            Fm.xo2 = 0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                Fm.x[j] = P.x[j];
+                Fm.vimp[j] = imp ? P.vimp[j] : 0.0;
+            }
+#pragma unroll
+            for (int prim = 0; prim < 2; ++prim) {
+                const DevShape& T = prim ? S2 : S1;
+                const double* th = prim ? th2 : th1;
+                double* gp = g + 6 * prim;
+                if (imp && imp_ok) Fm.imp_grad_prim(agA[prim], agZ[prim], T, prim, th, gp);
+                else if (A.flags & (F_GRAD_ENV | F_GRAD_IMP)) Fm.env_grad_prim(agZ[prim], T, prim, th, gp);
+                else Fm.fd_grad_prim(agZ[prim], T, prim, th, gp);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 12; ++c) g[c] = nan;
+        }
+    }
+    if (lane != 0) return;
+    const double al = ok ? P.x[3] : nan;
+    if (A.alpha) A.alpha[pi] = al;
+    if (A.iters) A.iters[pi] = it;
+    if (A.status) A.status[pi] = st;
+    if ((A.flags & F_CONTACT) && A.contact) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A.contact[c * B + pi] = ok ? P.x[c] : nan;
+    }
+    if (want_grad && A.grad) {
+#pragma unroll
+        for (int c = 0; c < 12; ++c) A.grad[c * B + pi] = g[c];
+    }
+    if (A.rec) {
+        double* const rec = A.rec + (int64_t)kRec * pi;
+        rec[0] = al;
+#pragma unroll
+        for (int c = 0; c < 12; ++c) rec[1 + c] = want_grad ? g[c] : nan;
+        rec[13] = rec_ints(st, it);
+    }
+}
+
+// One workgroup of one wave per plan slot (no barrier: a wave's LDS operations execute in
+// order); the slots of a streamed bucket are in descending row count (dcol_plan.hpp), so the
+// longest waves are dispatched first.
+constexpr int kStreamBlock = 64;
+template <int N, int NSOC>
+__global__ void __launch_bounds__(kStreamBlock, 1) prox_stream_kernel(KArgs A) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ double rowstate[kStreamLdsDoubles];
+    const int64_t slot = blockIdx.x;
+    if (slot >= A.n) return;
+    const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
+    using Slv = StreamSolver<N, NSOC, kStreamBlock>;
+    solve_stream<N, NSOC, kStreamBlock>(A, pi, (int)threadIdx.x, (typename Slv::lds_d*)rowstate);
+#endif
+}
+
 }  // namespace dcol

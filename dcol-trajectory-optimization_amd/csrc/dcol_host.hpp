@@ -14,6 +14,8 @@
 #include "dcol_device.hpp"
 #include "dcol_variants.inc"
 
+static_assert(dcol::kStreamMaxRows == DCOL_MAX_PAIR_ROWS, "streamed-row capacity");
+
 namespace dcol_host {
 using namespace dcol;
 
@@ -185,7 +187,18 @@ struct PairClass {
     int32_t status;   // OK / UNSUPPORTED / TOO_LARGE
     int N, nsoc, o, omax, lpp;
     int oe = 0;       // row-partitioned bucket: extra-row slots (0: dense-row kernels)
+    bool stream = false;   // above the register kernels' buckets: the streamed-row kernel
+                           // (omax = DCOL_MAX_PAIR_ROWS, lpp = 64: a wave per pair)
 };
+
+// the streamed-row kernel has an instance for (N, NSOC) (dcol_device.hpp DCOL_STREAM_SHAPES)
+inline bool stream_built(int N, int nsoc) {
+#define DCOL_SB(NN, NS) \
+    if (NN == N && NS == nsoc) return true;
+    DCOL_STREAM_SHAPES(DCOL_SB)
+#undef DCOL_SB
+    return false;
+}
 
 // DCOL_NO_PART=1: no row-partitioned kernels (A/B runs, tests)
 inline bool part_disabled() {
@@ -268,7 +281,12 @@ inline bool part_bucket(int N, int nsoc, int op, int oe, PairClass& c) {
 
 // case4: DCOL_PLAN_CASE4 extension (both primitives with extra columns: n = 4 + e1 + e2);
 // part: row-partitioned buckets allowed (DCOL_NO_PART unset)
-inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = false, bool part = !part_disabled()) {
+// stream: a pair of cases 1-3 with more rows than its (N, NSOC) bucket list holds, up to
+// DCOL_MAX_PAIR_ROWS, is OK and marked streamed (false: DCOL_TOO_LARGE, as for the contact-point
+// Jacobian's plans, which have no streamed copy).  A pair that fits a bucket keeps it; a
+// case-4 pair (both primitives with extra columns) above its list stays DCOL_TOO_LARGE.
+inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = false, bool part = !part_disabled(),
+                          bool stream = true) {
     PairClass c{DCOL_OK, 4, 0, 0, 0, 0};
     if (a.n_extra > 0 && b.n_extra > 0 && !case4) {   // combine_problem_matrices.py:58-67 (case 4)
         c.status = DCOL_UNSUPPORTED;
@@ -282,16 +300,19 @@ inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = fal
         if (part_bucket(c.N, c.nsoc, op, c.o - op, c)) return c;
     }
     auto it = buckets().find({c.N, c.nsoc});
-    if (it == buckets().end()) {
-        c.status = DCOL_TOO_LARGE;
+    if (it != buckets().end())
+        for (int om : it->second)
+            if (om >= std::max(c.o, 1)) {
+                c.omax = om;
+                c.lpp = choose_lpp(c.N, c.nsoc, om);
+                return c;
+            }
+    if (stream && !(a.n_extra > 0 && b.n_extra > 0) && c.o <= DCOL_MAX_PAIR_ROWS && stream_built(c.N, c.nsoc)) {
+        c.stream = true;
+        c.omax = DCOL_MAX_PAIR_ROWS;
+        c.lpp = 64;
         return c;
     }
-    for (int om : it->second)
-        if (om >= std::max(c.o, 1)) {
-            c.omax = om;
-            c.lpp = choose_lpp(c.N, c.nsoc, om);
-            return c;
-        }
     c.status = DCOL_TOO_LARGE;
     return c;
 }

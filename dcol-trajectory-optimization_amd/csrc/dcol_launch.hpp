@@ -37,6 +37,11 @@ hipError_t launch_part_n6s1(int omax, int oe, int lpp, int flags, const KArgs& a
 hipError_t launch_part_n6s2(int omax, int oe, int lpp, int flags, const KArgs& args, hipStream_t stream);
 hipError_t launch_part_n6s2_dense(int omax, int oe, int lpp, int flags, const KArgs& args, hipStream_t stream);
 
+// the streamed-row kernels (dcol_kernels_stream.hip; dcol_device.hpp DCOL_STREAM_SHAPES): one
+// workgroup of one wave per slot of [args.slot0, args.slot0 + args.n), pairs of up to
+// kStreamMaxRows orthant rows
+hipError_t launch_stream(int N, int nsoc, const KArgs& args, hipStream_t stream);
+
 // the contact-point Jacobian copies (dcol_kernels_jac.hip, one object per N): the dense-row
 // kernel of shape (N, nsoc, omax) at its DCOL_JAC_VARIANTS lanes per pair
 hipError_t launch_jac_n4(int nsoc, int omax, int lpp, const KArgs& args, hipStream_t stream);
@@ -110,7 +115,7 @@ hipError_t launch_pair_server(const KArgs& args, PairBox* box, int64_t idle_tick
         if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(dcol_exec_violations), &z, sizeof(z));   \
         return v;                                                                              \
     }
-#define DCOL_EXEC_TAGS(X) X(n4) X(n5) X(n6) X(n7) X(n8) X(fused) X(packed) X(p51) X(p52) X(p61) X(p62) X(p62d) X(susp) X(server) \
+#define DCOL_EXEC_TAGS(X) X(n4) X(n5) X(n6) X(n7) X(n8) X(fused) X(packed) X(p51) X(p52) X(p61) X(p62) X(p62d) X(susp) X(server) X(stream) \
     X(jac4) X(jac5) X(jac6) X(jac7) X(jac8)
 #define DCOL_EXEC_DECL(tag) unsigned long long exec_violations_##tag(bool reset);
 DCOL_EXEC_TAGS(DCOL_EXEC_DECL)

@@ -141,6 +141,12 @@ struct Bucket {
     int32_t code = 0;   // reject status
     int64_t slot0 = 0, n = 0;
     int lane = 0;   // 0 = caller's stream, 1..kSideStreams = side stream
+    // streamed bucket (PairClass::stream): the (N, nsoc) streamed-row kernel, a wave per pair
+    // (omax = DCOL_MAX_PAIR_ROWS, lpp = 64, dense SOC rows); its slots are in descending row
+    // count, and `rows` is the sum of its pairs' row counts rounded up to whole slots
+    // (bucket_cost)
+    bool stream = false;
+    int64_t rows = 0;
 };
 
 // What a plan will launch.
@@ -168,9 +174,10 @@ struct BucketKey {
     int kind, N, nsoc, omax, lpp;
     SocForm soc;
     int code, oe;
+    int stream = 0;   // 1: the streamed bucket of (N, nsoc), after its register buckets
     bool operator<(const BucketKey& o) const {
-        return std::tie(kind, N, nsoc, omax, lpp, soc, code, oe) <
-               std::tie(o.kind, o.N, o.nsoc, o.omax, o.lpp, o.soc, o.code, o.oe);
+        return std::tie(kind, N, nsoc, omax, lpp, soc, code, oe, stream) <
+               std::tie(o.kind, o.N, o.nsoc, o.omax, o.lpp, o.soc, o.code, o.oe, o.stream);
     }
 };
 
@@ -200,6 +207,7 @@ struct BucketMode {
 // buckets up to twice its rows (a tight bucket compiled only with LPP 2 -- 6 or 10 rows --
 // loses to the next bucket's 8-lane groups), fewer rows on ties.
 inline void latency_config(Bucket& L) {
+    if (L.stream) return;   // one configuration: a wave per pair
     if (L.oe > 0) {   // row-partitioned bucket: its largest compiled LPP
         L.lpp = part_lpp(L.N, L.nsoc, L.omax, L.oe, /*latency=*/true);
         return;
@@ -223,7 +231,15 @@ inline void latency_config(Bucket& L) {
 // benchmark of profiles/r03_soc/class_bench.log, within ~17 % on the 13 SOC classes): row
 // slots, SOC blocks (dense SOC rows cost more than the structured ball / cone rows) and the
 // N x N normal-matrix work; polytope x polytope buckets run at two waves per SIMD (x 0.5).
+// A streamed bucket: the same per-row-slot and per-block terms over its pairs' own row counts
+// (Bucket::rows) instead of n * omax, the row term doubled -- its rows are re-formed from
+// their descriptors in each of the iteration's four passes and it runs one wave per SIMD --
+// and the N x N term times 64, since the normal-matrix work a register kernel's lane does for
+// its own pair occupies a whole wave here.  An estimate from the kernel's structure, used
+// only to order and spread launches.
 inline double bucket_cost(const Bucket& L) {
+    if (L.stream)
+        return 2.0 * 0.0806 * (double)L.rows + (double)L.n * 64.0 * (0.27 * L.nsoc + 0.0139 * L.N * L.N);
     const bool dense_soc = L.nsoc > 0 && !(L.flags() & (LF_BALL | LF_CONE));
     const double per_pair = 0.0806 * L.omax + 0.127 * L.nsoc + 0.0139 * L.N * L.N + (dense_soc ? 0.143 * L.nsoc : 0.0);
     return (double)L.n * per_pair * (L.nsoc == 0 ? 0.5 : 1.0);
@@ -283,7 +299,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
     auto classify_pair = [&](int32_t i1, int32_t i2) -> int32_t {
         const DevShape& a = shapes[i1];
         const DevShape& b = shapes[i2];
-        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false) : classify(a, b, mode.case4);
+        // (a Jacobian plan has no streamed copy: its pairs above the buckets stay DCOL_TOO_LARGE)
+        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false, /*stream=*/false) : classify(a, b, mode.case4);
         if (mode.jac && c.status == DCOL_OK) c.lpp = jac_lpp(c.N, c.nsoc, c.omax);
         const bool none_cone = a.soc_kind != SOC_CONE && b.soc_kind != SOC_CONE;
         const bool all_cone = a.soc_kind != SOC_BALL && b.soc_kind != SOC_BALL;
@@ -293,7 +310,7 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
             c = classify(a, b, mode.case4, /*part=*/false);
         if (mode.lat_part && c.status == DCOL_OK && c.oe > 0 && part_lpp(c.N, c.nsoc, c.omax, c.oe, /*latency=*/true) < 2)
             c = classify(a, b, mode.case4, /*part=*/false);
-        const SocForm soc = mode.jac ? SocForm::Dense
+        const SocForm soc = (mode.jac || c.stream) ? SocForm::Dense   // (the streamed kernel's SOC rows are dense)
                             : c.nsoc == 0 ? ((a.boxp && b.boxp && c.N == 4 && c.omax == 12 && c.o == 12 && !pol.no_box)
                                                ? SocForm::Box : SocForm::Dense)
                             : (none_cone && !pol.no_ball) ? SocForm::Ball
@@ -306,8 +323,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
         // flavour's own list (row-partitioned buckets have theirs: PairClass::lpp)
         if (c.status == DCOL_OK && (soc == SocForm::Ball || soc == SocForm::Cone) && c.oe == 0)
             c.lpp = choose_lpp(c.N, c.nsoc, c.omax, soc == SocForm::Ball ? 2 : 4);
-        const BucketKey k = c.status == DCOL_OK ? BucketKey{0, c.N, c.nsoc, c.omax, c.lpp, soc, 0, c.oe}
-                                                : BucketKey{1, 0, 0, 0, 0, SocForm::Dense, c.status, 0};
+        const BucketKey k = c.status == DCOL_OK ? BucketKey{0, c.N, c.nsoc, c.omax, c.lpp, soc, 0, c.oe, c.stream ? 1 : 0}
+                                                : BucketKey{1, 0, 0, 0, 0, SocForm::Dense, c.status, 0, 0};
         auto it = gid_of_key.emplace(k, (int32_t)groups.size()).first;
         if (it->second == (int32_t)groups.size()) groups.push_back(Group{k});
         Group& g = groups[it->second];
@@ -342,9 +359,11 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
     // large mixed plan run side by side on the fan-out streams, so each keeps its throughput
     // configuration even when it alone would leave SIMDs idle (PlanPolicy::latency_per_launch:
     // the per-launch rule).
+    // (the register buckets' lanes: a streamed bucket has one configuration and does not
+    // change what the other buckets get -- plan_layout)
     int64_t plan_lanes = 0;
     for (const Group& G : groups)
-        if (G.key.kind == 0) plan_lanes += G.n * G.key.lpp;
+        if (G.key.kind == 0 && !G.key.stream) plan_lanes += G.n * G.key.lpp;
     p.small = !mode.force_large && plan_lanes < pol.small_lanes(simds);
     p.buckets.clear();
     p.perm.assign((size_t)B, 0);
@@ -365,6 +384,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
         L.ball = solve && G.key.soc == SocForm::Ball;
         L.cone = solve && G.key.soc == SocForm::Cone;
         L.box = solve && G.key.soc == SocForm::Box && L.full;
+        L.stream = solve && G.key.stream != 0;
+        if (L.stream) L.full = false;   // (no padding-free copy: the row count is a run-time value)
         L.slot0 = at;
         L.n = G.n;
         if (solve && !lpp_forced() && L.n * L.lpp < 64LL * simds && (p.small || pol.latency_per_launch))
@@ -373,6 +394,18 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
         p.buckets.push_back(L);
     }
     for (int64_t i = 0; i < B; ++i) p.perm[(size_t)groups[gid[(size_t)i]].at++] = (int32_t)i;   // stable
+    // A streamed bucket's slots in descending row count (stable): its launch is one wave per
+    // slot, handed out in slot order as SIMDs free up, so the longest waves start first and
+    // the short ones fill the tail -- the packed launch's list-scheduling argument, within a
+    // bucket.
+    for (Bucket& L : p.buckets) {
+        if (!L.stream) continue;
+        const auto rows_of = [&](int32_t pi) { return shapes[s1[pi]].n_ort + shapes[s2[pi]].n_ort; };
+        const auto first = p.perm.begin() + L.slot0, last = first + L.n;
+        std::stable_sort(first, last, [&](int32_t a, int32_t b) { return rows_of(a) > rows_of(b); });
+        L.rows = 0;
+        for (auto it = first; it != last; ++it) L.rows += (rows_of(*it) + 63) / 64 * 64;
+    }
     assign_lanes(p, pol);
     return DCOL_SUCCESS;
 }
@@ -385,7 +418,7 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
 inline bool plan_segments(PlanLayout& p, int (*vid_of)(int, int, int, int, int, int), const PlanPolicy& pol) {
     std::vector<int> order;
     for (size_t i = 0; i < p.buckets.size(); ++i)
-        if (p.buckets[i].kind == 0) order.push_back((int)i);
+        if (p.buckets[i].kind == 0 && !p.buckets[i].stream) order.push_back((int)i);
     if (!pol.fused_key_order)
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
             const Bucket& A = p.buckets[a];
@@ -408,12 +441,23 @@ inline bool plan_segments(PlanLayout& p, int (*vid_of)(int, int, int, int, int, 
     return true;
 }
 
-// solve buckets of a layout and their lanes together
-inline std::pair<int, int64_t> solve_lanes(const PlanLayout& p) {
+// A plan with a streamed bucket takes the per-bucket launch form, never fused or packed (the
+// fused and packed kernels switch over register-kernel cases only).  Its other buckets keep
+// their configuration: the policy below looks at the register buckets alone (solve_lanes,
+// plan_segments), so they are bucketed and configured exactly as in the plan of the same
+// pairs without the streamed ones, and plan_layout then launches every bucket by itself.
+inline bool has_stream(const PlanLayout& p) {
+    for (const Bucket& L : p.buckets)
+        if (L.stream) return true;
+    return false;
+}
+
+// register solve buckets of a layout and their lanes together (stream: the streamed ones too)
+inline std::pair<int, int64_t> solve_lanes(const PlanLayout& p, bool stream = false) {
     int solves = 0;
     int64_t lanes = 0;
     for (const Bucket& L : p.buckets)
-        if (L.kind == 0) {
+        if (L.kind == 0 && (stream || !L.stream)) {
             ++solves;
             lanes += L.n * L.lpp;
         }
@@ -467,7 +511,8 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
     // still does not fuse, the first bucketing stands
     bool only_part = true;
     for (const Bucket& L : out.buckets)
-        if (L.kind == 0 && L.oe == 0 && fused_vid(L.N, L.nsoc, L.omax, L.lpp, L.flags(), 0) < 0) only_part = false;
+        if (L.kind == 0 && L.oe == 0 && !L.stream && fused_vid(L.N, L.nsoc, L.omax, L.lpp, L.flags(), 0) < 0)
+            only_part = false;
     if (plan_fuse(out, simds, pol) == 2 && only_part) {
         mode.fused_part = true;
         rc = bucket_pairs(shapes, simds, B, s1, s2, mode, pol, out);
@@ -502,6 +547,15 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
                 out = std::move(q);
             }
         }
+    }
+    // With a streamed bucket: the same buckets, launched one by one over the streams (as under
+    // DCOL_PLAN_NO_FUSE); whether the plan can fill the GPU counts the streamed waves too.
+    if (has_stream(out)) {
+        out.segs.clear();
+        out.fused_blocks = 0;
+        out.packed = false;
+        out.small = solve_lanes(out, /*stream=*/true).second < pol.small_lanes(simds);
+        assign_lanes(out, pol);
     }
     return DCOL_SUCCESS;
 }

@@ -25,6 +25,7 @@ PLAN_CASE4, PLAN_NO_FUSE, PLAN_SUSPEND, PLAN_JACOBIAN = 1, 2, 4, 8
 SUCCESS, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3
 ABI_VERSION = 5
 PAIR_PLANS_MAX = 64   # DCOL_PAIR_PLANS_MAX
+MAX_PAIR_ROWS = 1024  # DCOL_MAX_PAIR_ROWS
 
 
 class DcolLibraryError(RuntimeError):

@@ -60,7 +60,8 @@ def raise_for_status(status: int):
     if status == _lib.NONFINITE:
         raise ValueError("array must not contain infs or NaNs")                  # scipy check_finite
     if status == _lib.TOO_LARGE:
-        raise ValueError("pair exceeds the engine's orthant-row capacity (128 rows, 64 per primitive)")
+        raise ValueError(f"pair exceeds the engine's orthant-row capacity ({_lib.MAX_PAIR_ROWS} rows for the two primitives "
+                         "together; 32 for a case-4 pair, 128 with the contact-point Jacobian)")
     raise RuntimeError(f"unknown dcol status {status}")
 
 

@@ -63,8 +63,16 @@ enum dcol_status {
     DCOL_UNSUPPORTED = 2, /* both primitives have extra columns (combine case 4)          */
     DCOL_NOT_PD = 3,      /* Cholesky of G'G or of the NT normal matrix failed            */
     DCOL_NONFINITE = 4,   /* a non-finite value reached a factorisation                   */
-    DCOL_TOO_LARGE = 5    /* more orthant rows than the engine's row capacity (128)       */
+    DCOL_TOO_LARGE = 5    /* more orthant rows than the engine's row capacity: DCOL_MAX_PAIR_ROWS
+                             for a pair of combine cases 1-3; 32 for a case-4 pair (DCOL_PLAN_CASE4);
+                             128 in a DCOL_PLAN_JACOBIAN plan and dcol_prox_jacobian_host          */
 };
+
+/* Orthant rows a pair's two primitives may bring together (polytope faces, polygon edges, the
+ * few rows of a cone / capsule / cylinder).  Pairs of up to 128 rows run the register kernels
+ * of their row bucket; pairs above that run the streamed-row kernel (one wave per pair, rows
+ * indexed at run time, row state in LDS).                             */
+#define DCOL_MAX_PAIR_ROWS 1024
 
 /* dcol_plan_run / dcol_prox_batch_host flags. */
 enum dcol_flags {
@@ -173,7 +181,10 @@ int dcol_plan_num_buckets(const dcol_plan* plan, int32_t* n);  /* variant bucket
 /* How a run launches its solve buckets: DCOL_FORM_BUCKETS one launch per bucket (over
  * dcol_plan_num_streams streams), DCOL_FORM_FUSED one fused launch (a small plan: latency
  * configurations), DCOL_FORM_PACKED one packed launch (a mid-size plan: throughput
- * configurations).                                                   */
+ * configurations).  A plan with a streamed bucket -- pairs of 129 to
+ * DCOL_MAX_PAIR_ROWS orthant rows; dcol_plan_bucket reports it with [3] = DCOL_MAX_PAIR_ROWS and
+ * [4] = 64 lanes per pair, its slots in descending row count -- always takes
+ * DCOL_FORM_BUCKETS.                                                                       */
 enum dcol_plan_form { DCOL_FORM_BUCKETS = 0, DCOL_FORM_FUSED = 1, DCOL_FORM_PACKED = 2 };
 int dcol_plan_launch_form(const dcol_plan* plan, int32_t* form);
 /* Bucket i (0 <= i < dcol_plan_num_buckets) of a plan, for tests and tools: info[0] kind (0 a
