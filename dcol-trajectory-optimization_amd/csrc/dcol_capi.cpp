@@ -504,8 +504,8 @@ int ensure_fanout(const dcol_table* tc, dcol_plan* p) {
 
 // The plan's layout under the process's policy, and its launches
 int plan_build(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, bool case4, bool allow_fuse,
-               dcol_plan* p, bool jac = false) {
-    const int rc = jac ? plan_layout_jac(t->shapes, t->simds, B, s1, s2, case4, plan_policy(), p->lay)
+               dcol_plan* p, bool jac = false, bool jac_stream = false) {
+    const int rc = jac ? plan_layout_jac(t->shapes, t->simds, B, s1, s2, case4, plan_policy(), p->lay, jac_stream)
                        : plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay);
     if (rc != DCOL_SUCCESS) return rc;
     p->jac = jac;
@@ -525,8 +525,10 @@ int dcol_plan_create(const dcol_table* t, int64_t B, const int32_t* s1, const in
 int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, int32_t options,
                         dcol_plan** out) {
     if (!t || !out || B < 0 || (B > 0 && (!s1 || !s2))) return fail(DCOL_ERR_ARG, "dcol_plan_create: bad arguments");
-    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND | DCOL_PLAN_JACOBIAN))
+    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND | DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM))
         return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: unknown option bits");
+    if ((options & DCOL_PLAN_JACOBIAN_STREAM) && !(options & DCOL_PLAN_JACOBIAN))
+        return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: DCOL_PLAN_JACOBIAN_STREAM needs DCOL_PLAN_JACOBIAN");
     if ((options & DCOL_PLAN_JACOBIAN) && (options & DCOL_PLAN_SUSPEND))
         return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: DCOL_PLAN_JACOBIAN cannot be combined with DCOL_PLAN_SUSPEND");
     if (B > INT32_MAX) return fail(DCOL_ERR_ARG, "dcol_plan_create: B exceeds 2^31-1");
@@ -534,7 +536,7 @@ int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const
     auto* p = new (std::nothrow) dcol_plan();
     if (!p) return fail(DCOL_ERR_NOMEM, "host allocation failed");
     int rc = plan_build(t, B, s1, s2, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0, p,
-                        (options & DCOL_PLAN_JACOBIAN) != 0);
+                        (options & DCOL_PLAN_JACOBIAN) != 0, (options & DCOL_PLAN_JACOBIAN_STREAM) != 0);
     if (rc != DCOL_SUCCESS) {
         delete p;
         return rc;
@@ -715,7 +717,8 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     // time (DCOL_PAIR_SERVER_IDLE_US) -- asking it to leave now costs a restart instead.
     if (yield && (!p->lay.small || stream == nullptr)) yield_pair_servers(p->table->device);
     // The contact-point Jacobian: jac is set by dcol_plan_run_jac alone, after its checks, and
-    // then the plan's dense-row buckets launch their Jacobian copies.  The kernels' F_JAC bit
+    // then the plan's dense-row buckets launch their Jacobian copies (the streamed buckets of a
+    // DCOL_PLAN_JACOBIAN_STREAM plan: the streamed kernels' Jacobian copies).  The kernels' F_JAC bit
     // follows jac, so DCOL_JACOBIAN in any other caller's flags is dropped here (it had no
     // meaning before ABI 5).
     const bool want_jac = jac != nullptr;
@@ -791,8 +794,8 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
             b.susp_cap = L.susp_cap;
             e = hipMemsetAsync(L.d_susp_count, 0, sizeof(int32_t), ls);
             if (e == hipSuccess) e = launch_susp(L.N, L.nsoc, L.omax, L.lpp, L.flags(), L.oe, b, ls);
-        } else if (want_jac) {   // (a Jacobian plan: dense rows, no hint)
-            e = launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls);
+        } else if (want_jac) {   // (a Jacobian plan: dense rows or a streamed bucket's JAC copy, no hint)
+            e = L.stream ? launch_stream_jac(L.N, L.nsoc, a, ls) : launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls);
         } else if (L.stream) {   // a wave per pair: nothing to regroup, so no hint
             e = launch_stream(L.N, L.nsoc, a, ls);
         } else {
@@ -1205,6 +1208,7 @@ int dcol_debug_exec_selftest(uint64_t* counted) {
 
 // dcol_prox_batch_host, and with jac (host [B][4][12]) dcol_prox_jacobian_host: the same
 // staging with 48 B more output doubles behind the gradient, a DCOL_PLAN_JACOBIAN layout
+// (DCOL_JACOBIAN_STREAM in flags: with DCOL_PLAN_JACOBIAN_STREAM)
 static int prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, const int32_t* s2, const double* pose1,
                            const double* pose2, double tol, int32_t max_iter, int32_t flags, double* alpha,
                            double* contact, double* grad, double* jac, int32_t* iters, int32_t* status) {
@@ -1215,7 +1219,10 @@ static int prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, c
     dcol_table* t = const_cast<dcol_table*>(tc);
     std::lock_guard<std::mutex> lk(t->mu);
     dcol_plan p;   // transient, device arrays are views into the table's staging buffer
-    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p, jac != nullptr);
+    // (DCOL_JACOBIAN_STREAM: a host-call flag like DCOL_CASE4, not a kernel flag)
+    const bool jac_stream = jac != nullptr && (flags & DCOL_JACOBIAN_STREAM) != 0;
+    flags &= ~DCOL_JACOBIAN_STREAM;
+    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p, jac != nullptr, jac_stream);
     if (rc != DCOL_SUCCESS) return rc;
     rc = ensure_fanout(t, &p);
     if (rc != DCOL_SUCCESS) return rc;

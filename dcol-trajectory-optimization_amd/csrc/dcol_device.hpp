@@ -2447,6 +2447,11 @@ struct Solver {
         for (int j = 0; j < N; ++j)
 #pragma unroll
             for (int c = 0; c < N; ++c) F.A[c][j] = R::sum(Hm[j][c]);   // A = H'
+        return jacobian_lu(F);
+    }
+    // The elimination: F.A holds the summed H' on entry, the factor on return (shared with the
+    // streamed solver, StreamSolver::jacobian_factor).  False if a pivot is zero or not finite.
+    DCOL_HD static bool jacobian_lu(JacLU& F) {
         bool ok = true;
 #pragma unroll
         for (int j = 0; j < N; ++j) F.pr[j] = j;
@@ -2478,9 +2483,8 @@ struct Solver {
         }
         return ok;
     }
-    // Output row k: v_k = H^-T e_k into vimp (L U v = P e_k) and the per-row weights
-    // a_k = -D'G v_k into wts (lane rows, like z)
-    DCOL_HD void jacobian_adjoints(const JacLU& F, int k, double* wts) {
+    // v = H^-T e_k by the two triangular solves (L U v = P e_k)
+    DCOL_HD static void jacobian_solve(const JacLU& F, int k, double (&v)[N]) {
         double y[N];
 #pragma unroll
         for (int r = 0; r < N; ++r) {
@@ -2493,9 +2497,14 @@ struct Solver {
         for (int r = N - 1; r >= 0; --r) {
             double t = y[r];
 #pragma unroll
-            for (int c = r + 1; c < N; ++c) t -= F.A[r][c] * vimp[c];
-            vimp[r] = t * F.ip[r];
+            for (int c = r + 1; c < N; ++c) t -= F.A[r][c] * v[c];
+            v[r] = t * F.ip[r];
         }
+    }
+    // Output row k: v_k = H^-T e_k into vimp and the per-row weights a_k = -D'G v_k into wts
+    // (lane rows, like z)
+    DCOL_HD void jacobian_adjoints(const JacLU& F, int k, double* wts) {
+        jacobian_solve(F, k, vimp);
 #pragma unroll
         for (int i = 0; i < OR; ++i) {
             const double d = vort(i) ? z[i] * frcp(s[i]) : 0.0;
@@ -3548,9 +3557,14 @@ struct StreamSolver {
     }
     // The two primitives' aggregates (Solver::lag_aggregate) in one pass over the rows: with
     // the duals z as weights (agZ) and, imp: also with the implicit mode's a = -W^-2 G v
-    // (agA; W: implicit_v's scalings)
+    // (agA; W: implicit_v's scalings).  JACW (the JAC instances' Jacobian phase): agA with the
+    // contact-point Jacobian's weights a = -D'G v instead, D' u = z o (s \ u) -- z / s on an
+    // orthant row in the JAC copies' reciprocal form -- for the v in vimp; the weights are
+    // formed inside the pass, nothing per row is stored.  WZ = false leaves agZ as it is.
+    template <bool JACW = false, bool WZ = true>
     DCOL_HD void aggregates(const DevShape& S1, const DevShape& S2, bool imp, const SocNT* W, Agg (&agZ)[2],
                             Agg (&agA)[2]) const {
+        const bool wgt = JACW || imp;
         double uz[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, ua[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
         for (int k = 0; k < nslot; ++k) {
             const int i = k * LANES + lane;
@@ -3559,11 +3573,15 @@ struct StreamSolver {
                 row(i, g, h);
                 const bool p2 = i >= o1;
                 const double sk = fld(FS_, k), zk = fld(FZ_, k);
-                const double wa = imp ? -((zk * (zk * frcp1(sk * zk))) * dotn(g, vimp)) : 0.0;
+                double wa;
+                if constexpr (JACW) wa = -((zk * frcp(sk)) * dotn(g, vimp));
+                else wa = imp ? -((zk * (zk * frcp1(sk * zk))) * dotn(g, vimp)) : 0.0;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    uz[0][c] = fma(p2 ? 0.0 : zk, g[c], uz[0][c]);
-                    uz[1][c] = fma(p2 ? zk : 0.0, g[c], uz[1][c]);
+                    if constexpr (WZ) {
+                        uz[0][c] = fma(p2 ? 0.0 : zk, g[c], uz[0][c]);
+                        uz[1][c] = fma(p2 ? zk : 0.0, g[c], uz[1][c]);
+                    }
                     ua[0][c] = fma(p2 ? 0.0 : wa, g[c], ua[0][c]);
                     ua[1][c] = fma(p2 ? wa : 0.0, g[c], ua[1][c]);
                 }
@@ -3572,23 +3590,33 @@ struct StreamSolver {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const int kind = NSOC > 0 ? (p ? S2.soc_kind : S1.soc_kind) : SOC_NONE;
-            agZ[p].kind = agA[p].kind = kind;
+            agA[p].kind = kind;
+            if constexpr (WZ) agZ[p].kind = kind;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                agZ[p].u[c] = R::sum(uz[p][c]);
-                agA[p].u[c] = imp ? R::sum(ua[p][c]) : 0.0;
+                if constexpr (WZ) agZ[p].u[c] = R::sum(uz[p][c]);
+                agA[p].u[c] = wgt ? R::sum(ua[p][c]) : 0.0;
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) agZ[p].zs[e] = agA[p].zs[e] = 0.0;
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (WZ) agZ[p].zs[e] = 0.0;
+                agA[p].zs[e] = 0.0;
+            }
         }
 #pragma unroll
         for (int b = 0; b < NSOC; ++b) {
             double wa[4] = {0.0, 0.0, 0.0, 0.0};
-            if (imp) {
+            if (wgt) {
                 double u[4], t[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) u[e] = dotn(Gs[b][e], vimp);
-                soc_w2inv(W[b], u, t);
+                if constexpr (JACW) {   // D_b' u = z o (s \ u)
+                    double su[4];
+                    soc_iprod(ss[b], u, su);
+                    soc_prod(zs[b], su, t);
+                } else {
+                    soc_w2inv(W[b], u, t);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) wa[e] = -t[e];
             }
@@ -3597,12 +3625,12 @@ struct StreamSolver {
                 if (soc_owner[b] != p) continue;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    agZ[p].zs[e] = zs[b][e];
+                    if constexpr (WZ) agZ[p].zs[e] = zs[b][e];
                     agA[p].zs[e] = wa[e];
                     if (soc_kind[b] == SOC_CONE) {   // cone rows: Qe(-E e_k)
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
-                            agZ[p].u[c] = fma(zs[b][e], Gs[b][e][c], agZ[p].u[c]);
+                            if constexpr (WZ) agZ[p].u[c] = fma(zs[b][e], Gs[b][e][c], agZ[p].u[c]);
                             agA[p].u[c] = fma(wa[e], Gs[b][e][c], agA[p].u[c]);
                         }
                     }
@@ -3610,12 +3638,87 @@ struct StreamSolver {
             }
         }
     }
+
+    // -------- contact-point Jacobian (the JAC instances) ---------------------------------
+    // Solver::jacobian_factor over streamed rows: H = G'D G at the returned iterate, D = z / s
+    // on an orthant row (re-formed in this one pass; the upper triangle per lane, then the wave
+    // sum) and D_b u = s \ (z o u) on a SOC block, whose non-symmetric share is added once
+    // after the reduction; then the shared elimination of H'.  False if a pivot is zero or not
+    // finite.
+    using JacLU = typename FS::JacLU;
+    DCOL_HD bool jacobian_factor(JacLU& F) const {
+        double Hm[N][N];
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = j; c < N; ++c) Hm[j][c] = 0.0;
+        for (int k = 0; k < nslot; ++k) {
+            const int i = k * LANES + lane;
+            if (i < o) {
+                double g[N], h;
+                row(i, g, h);
+                const double d = fld(FZ_, k) * frcp(fld(FS_, k));
+                double gd[N];
+#pragma unroll
+                for (int j = 0; j < N; ++j) gd[j] = g[j] * d;
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+#pragma unroll
+                    for (int c = j; c < N; ++c) Hm[j][c] += gd[j] * g[c];
+            }
+        }
+        allsum_sym(Hm);
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = 0; c < j; ++c) Hm[j][c] = Hm[c][j];
+#pragma unroll
+        for (int b = 0; b < NSOC; ++b)   // column c of D_b G_b, then G_b' of it
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                double col[4], zc[4], t[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) col[e] = Gs[b][e][c];
+                soc_prod(zs[b], col, zc);
+                soc_iprod(ss[b], zc, t);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < N; ++j) Hm[j][c] += Gs[b][e][j] * t[e];
+            }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int c = 0; c < N; ++c) F.A[c][j] = Hm[j][c];   // A = H'
+        return FS::jacobian_lu(F);
+    }
+    // The four adjoint vectors v_k = H^-T e_k (Solver::jacobian_solve, replicated in every
+    // lane), parked in the lane's own elements of the two fields the iteration used as
+    // temporaries (c, u: dead after the PDIP loop), so that the factor is not held across the
+    // output rows' passes: element t = k N + j of the 2 x 16 a lane owns at 64 lanes.
+    static_assert(4 * N <= 32 && SLOTS >= 16 && FU_ == FC_ + 1, "the parked v_k fit a lane's c and u elements");
+    DCOL_HD lds_d& parked(int t) const { return fld(FC_ + t / 16, t % 16); }
+    DCOL_HD void jacobian_park(const JacLU& F) {
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+            double v[N];
+            FS::jacobian_solve(F, k, v);
+#pragma unroll
+            for (int j = 0; j < N; ++j) parked(k * N + j) = v[j];
+        }
+    }
+    DCOL_HD void jacobian_fetch(int k) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) vimp[j] = parked(k * N + j);
+    }
 };
 
 // One pair by the streamed-row solver; every lane of the wave calls it (lane = 0 in the
 // one-lane build).  ws: the pair's row state, kStreamLdsDoubles doubles (the workgroup's
 // LDS).  Writes what solve_one writes, from lane 0.
-template <int N, int NSOC, int LANES>
+// JAC: the instance that can also write the contact-point Jacobian (KArgs::jac, F_JAC;
+// dcol_kernels_stream_jac.hip); the plain instances compile none of it.
+template <int N, int NSOC, int LANES, bool JAC = false>
 DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamSolver<N, NSOC, LANES>::lds_d* ws) {
     using Slv = StreamSolver<N, NSOC, LANES>;
     const int64_t B = A.B;
@@ -3647,13 +3750,14 @@ DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamS
     const bool ok = st == ST_OK;
     double g[12];
     const bool want_grad = (A.flags & (F_GRAD_FD | F_GRAD_ENV | F_GRAD_IMP)) && (A.grad || A.rec);
+    using Agg = typename Slv::Agg;
+    Agg agZ[2];   // (JAC: shared with the Jacobian phase when a gradient is asked too)
     if (want_grad) {
         if (ok) {
-            using Agg = typename Slv::Agg;
             const bool imp = (A.flags & F_GRAD_IMP) != 0;
             SocNT W[Slv::SSA];
             const bool imp_ok = imp && P.implicit_v(W);
-            Agg agZ[2], agA[2];
+            Agg agA[2];
             P.aggregates(S1, S2, imp, W, agZ, agA);
             typename Slv::FS Fm;   // the formulas read x, vimp and the (zero) column offset only
             Fm.q = 0;
@@ -3675,6 +3779,53 @@ DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamS
         } else {
 #pragma unroll
             for (int c = 0; c < 12; ++c) g[c] = nan;
+        }
+    }
+    if constexpr (JAC) {
+        // The contact-point Jacobian, a phase of its own after the gradient's (nothing of it is
+        // live in the PDIP loop: the rows are re-formed, the weights formed inside the pass
+        // that uses them).  One pass for H = G'D G, the replicated LU and the four pairs of
+        // triangular solves (the v_k parked in LDS: jacobian_park), then per output row k one
+        // pass for the weights' aggregates; with the z aggregates' pass (shared with the
+        // gradient when one is asked) six passes at most.
+        if ((A.flags & F_JAC) && A.jac) {
+            bool fine = false;
+            if (ok) {
+                {
+                    typename Slv::JacLU F;
+                    fine = P.jacobian_factor(F);
+                    if (fine) P.jacobian_park(F);
+                }
+                if (fine) {
+                    Agg agA[2];
+                    if (!want_grad) P.aggregates(S1, S2, false, nullptr, agZ, agA);
+                    typename Slv::FS Fm;
+                    Fm.q = 0;
+                    Fm.xo2 = 0;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) Fm.x[j] = P.x[j];
+#pragma unroll 1
+                    for (int k = 0; k < 4; ++k) {
+                        P.jacobian_fetch(k);
+                        P.template aggregates<true, false>(S1, S2, false, nullptr, agZ, agA);
+#pragma unroll
+                        for (int j = 0; j < N; ++j) Fm.vimp[j] = P.vimp[j];
+#pragma unroll
+                        for (int prim = 0; prim < 2; ++prim) {
+                            double jr[6];
+                            Fm.imp_grad_prim(agA[prim], agZ[prim], prim ? S2 : S1, prim, prim ? th2 : th1, jr);
+                            if (lane == 0) {
+#pragma unroll
+                                for (int c = 0; c < 6; ++c) A.jac[(int64_t)(12 * k + 6 * prim + c) * B + pi] = jr[c];
+                            }
+                        }
+                    }
+                }
+            }
+            if (!fine && lane == 0) {   // status not OK, or a zero / non-finite pivot: NaN in all 48
+#pragma unroll 1
+                for (int c = 0; c < 48; ++c) A.jac[(int64_t)c * B + pi] = nan;
+            }
         }
     }
     if (lane != 0) return;
@@ -3703,7 +3854,7 @@ DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamS
 // order); the slots of a streamed bucket are in descending row count (dcol_plan.hpp), so the
 // longest waves are dispatched first.
 constexpr int kStreamBlock = 64;
-template <int N, int NSOC>
+template <int N, int NSOC, bool JAC = false>
 __global__ void __launch_bounds__(kStreamBlock, 1) prox_stream_kernel(KArgs A) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ double rowstate[kStreamLdsDoubles];
@@ -3711,7 +3862,7 @@ __global__ void __launch_bounds__(kStreamBlock, 1) prox_stream_kernel(KArgs A) {
     if (slot >= A.n) return;
     const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
     using Slv = StreamSolver<N, NSOC, kStreamBlock>;
-    solve_stream<N, NSOC, kStreamBlock>(A, pi, (int)threadIdx.x, (typename Slv::lds_d*)rowstate);
+    solve_stream<N, NSOC, kStreamBlock, JAC>(A, pi, (int)threadIdx.x, (typename Slv::lds_d*)rowstate);
 #endif
 }
 

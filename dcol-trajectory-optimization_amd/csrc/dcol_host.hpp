@@ -283,7 +283,7 @@ inline bool part_bucket(int N, int nsoc, int op, int oe, PairClass& c) {
 // part: row-partitioned buckets allowed (DCOL_NO_PART unset)
 // stream: a pair of cases 1-3 with more rows than its (N, NSOC) bucket list holds, up to
 // DCOL_MAX_PAIR_ROWS, is OK and marked streamed (false: DCOL_TOO_LARGE, as for the contact-point
-// Jacobian's plans, which have no streamed copy).  A pair that fits a bucket keeps it; a
+// Jacobian's plans made without DCOL_PLAN_JACOBIAN_STREAM).  A pair that fits a bucket keeps it; a
 // case-4 pair (both primitives with extra columns) above its list stays DCOL_TOO_LARGE.
 inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = false, bool part = !part_disabled(),
                           bool stream = true) {

@@ -41,6 +41,9 @@ hipError_t launch_part_n6s2_dense(int omax, int oe, int lpp, int flags, const KA
 // workgroup of one wave per slot of [args.slot0, args.slot0 + args.n), pairs of up to
 // kStreamMaxRows orthant rows
 hipError_t launch_stream(int N, int nsoc, const KArgs& args, hipStream_t stream);
+// their contact-point Jacobian copies (dcol_kernels_stream_jac.hip): the same grid, for a run
+// with DCOL_JACOBIAN of a plan made with DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM
+hipError_t launch_stream_jac(int N, int nsoc, const KArgs& args, hipStream_t stream);
 
 // the contact-point Jacobian copies (dcol_kernels_jac.hip, one object per N): the dense-row
 // kernel of shape (N, nsoc, omax) at its DCOL_JAC_VARIANTS lanes per pair
@@ -116,7 +119,7 @@ hipError_t launch_pair_server(const KArgs& args, PairBox* box, int64_t idle_tick
         return v;                                                                              \
     }
 #define DCOL_EXEC_TAGS(X) X(n4) X(n5) X(n6) X(n7) X(n8) X(fused) X(packed) X(p51) X(p52) X(p61) X(p62) X(p62d) X(susp) X(server) X(stream) \
-    X(jac4) X(jac5) X(jac6) X(jac7) X(jac8)
+    X(stream_jac) X(jac4) X(jac5) X(jac6) X(jac7) X(jac8)
 #define DCOL_EXEC_DECL(tag) unsigned long long exec_violations_##tag(bool reset);
 DCOL_EXEC_TAGS(DCOL_EXEC_DECL)
 DCOL_EXEC_DECL(capi)   // the C-ABI unit's own counter (dcol_debug_exec_selftest)

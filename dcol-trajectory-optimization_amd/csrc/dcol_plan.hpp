@@ -200,6 +200,10 @@ struct BucketMode {
     // cone / box form, whatever the policy says) at the lanes per pair of its shape's
     // Jacobian copy (jac_lpp); set together with force_large (plan_layout_jac)
     bool jac = false;
+    // DCOL_PLAN_JACOBIAN_STREAM (with jac): pairs of cases 1-3 above the dense-row buckets, up
+    // to DCOL_MAX_PAIR_ROWS rows, are classified streamed as in a plain plan and run the
+    // streamed kernels' Jacobian copies; without it they stay DCOL_TOO_LARGE
+    bool jac_stream = false;
 };
 
 // A launch too small to fill the GPU runs the configuration with the shortest per-pair
@@ -299,9 +303,11 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
     auto classify_pair = [&](int32_t i1, int32_t i2) -> int32_t {
         const DevShape& a = shapes[i1];
         const DevShape& b = shapes[i2];
-        // (a Jacobian plan has no streamed copy: its pairs above the buckets stay DCOL_TOO_LARGE)
-        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false, /*stream=*/false) : classify(a, b, mode.case4);
-        if (mode.jac && c.status == DCOL_OK) c.lpp = jac_lpp(c.N, c.nsoc, c.omax);
+        // (a Jacobian plan's pairs above the buckets stay DCOL_TOO_LARGE unless it opted into
+        // the streamed Jacobian copies: BucketMode::jac_stream)
+        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false, /*stream=*/mode.jac_stream)
+                               : classify(a, b, mode.case4);
+        if (mode.jac && c.status == DCOL_OK && !c.stream) c.lpp = jac_lpp(c.N, c.nsoc, c.omax);
         const bool none_cone = a.soc_kind != SOC_CONE && b.soc_kind != SOC_CONE;
         const bool all_cone = a.soc_kind != SOC_BALL && b.soc_kind != SOC_BALL;
         if (mode.fused_part && c.status == DCOL_OK && c.oe > 0 &&
@@ -563,17 +569,21 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
 // The layout of a DCOL_PLAN_JACOBIAN plan: the pairs bucketed on the dense-row kernels
 // (BucketMode::jac), one launch per bucket over the streams of a plan that fills the GPU --
 // never fused or packed, no latency configurations (the Jacobian copies exist at one lane
-// count per shape).
+// count per shape).  stream (DCOL_PLAN_JACOBIAN_STREAM): pairs above the dense-row buckets get
+// a streamed bucket per (N, NSOC) as in a plain plan -- slots in descending row count, costed
+// by bucket_cost's streamed branch, spread over the streams with the other buckets -- and
+// the pairs of at most 128 rows the dense buckets they get without it.
 inline int plan_layout_jac(const std::vector<DevShape>& shapes, int simds, int64_t B, const int32_t* s1,
-                           const int32_t* s2, bool case4, const PlanPolicy& pol, PlanLayout& out) {
+                           const int32_t* s2, bool case4, const PlanPolicy& pol, PlanLayout& out, bool stream = false) {
     BucketMode mode;
     mode.case4 = case4;
     mode.force_large = true;
     mode.jac = true;
+    mode.jac_stream = stream;
     const int rc = bucket_pairs(shapes, simds, B, s1, s2, mode, pol, out);
     // (bucketed as a large plan; whether it can fill the GPU still decides if a run asks a
-    // resident pair server to leave)
-    if (rc == DCOL_SUCCESS) out.small = solve_lanes(out).second < pol.small_lanes(simds);
+    // resident pair server to leave: the streamed waves count, as in plan_layout)
+    if (rc == DCOL_SUCCESS) out.small = solve_lanes(out, /*stream=*/true).second < pol.small_lanes(simds);
     return rc;
 }
 

@@ -19,9 +19,11 @@ POLYTOPE, SPHERE, CONE, CAPSULE, CYLINDER, POLYGON = range(6)
 OK, MAXITER, UNSUPPORTED, NOT_PD, NONFINITE, TOO_LARGE = range(6)
 # enum dcol_flags
 GRAD_FD, GRAD_ENVELOPE, CONTACT, CASE4, GRAD_IMPLICIT, NO_GATHER, JACOBIAN = 1, 2, 4, 8, 16, 32, 64
+JACOBIAN_STREAM = 128   # dcol_prox_jacobian_host only: the streamed Jacobian copies (pairs of 129-1,024 rows)
 GRAD_ANY = GRAD_FD | GRAD_ENVELOPE | GRAD_IMPLICIT
 # enum dcol_plan_options
 PLAN_CASE4, PLAN_NO_FUSE, PLAN_SUSPEND, PLAN_JACOBIAN = 1, 2, 4, 8
+PLAN_JACOBIAN_STREAM = 16   # only with PLAN_JACOBIAN
 SUCCESS, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3
 ABI_VERSION = 5
 PAIR_PLANS_MAX = 64   # DCOL_PAIR_PLANS_MAX

@@ -106,18 +106,31 @@ class Table:
             self.handle = None
 
 
+def jacobian_mode(jacobian):
+    """The jacobian= argument of Plan / Engine.plan / Engine.solve_host: False, True (pairs of
+    at most 128 orthant rows, the default Jacobian plan) or "stream" (also pairs of 129 to
+    1,024 rows, on the streamed-row kernels' Jacobian copies) -> False, True or "stream"."""
+    if isinstance(jacobian, str):
+        if jacobian != "stream":
+            raise ValueError(f"jacobian must be False, True or 'stream', not {jacobian!r}")
+        return "stream"
+    return bool(jacobian)
+
+
 class Plan:
     """Owning wrapper of a dcol_plan: a fixed pairing bucketed by kernel variant."""
 
     def __init__(self, table: Table, s1, s2, case4: bool = False, fuse: bool = True, suspend: bool = False,
-                 jacobian: bool = False):
+                 jacobian=False):
         """case4=True: solve case-4 pairs (DCOL_PLAN_CASE4 extension) instead of reporting
         UNSUPPORTED like the reference.  fuse=False: one launch per variant bucket even for
         a small mixed plan (DCOL_PLAN_NO_FUSE; A/B and tests).  suspend=True: large buckets
         run as a suspend / resume launch pair (DCOL_PLAN_SUSPEND; bitwise the same results;
         the plan owns scratch -- do not run it on two streams at once).  jacobian=True: the plan
         can run(jacobian=True) (DCOL_PLAN_JACOBIAN: dense-row buckets, one launch each; not
-        with suspend)."""
+        with suspend); pairs above 128 orthant rows are TOO_LARGE in it.  jacobian="stream":
+        the same plus DCOL_PLAN_JACOBIAN_STREAM -- pairs of 129 to 1,024 rows get a streamed
+        bucket and run(jacobian=True) writes their Jacobian too (self.jacobian == "stream")."""
         lib = _lib.load()
         self.s1 = np.ascontiguousarray(s1, dtype=np.int32)
         self.s2 = np.ascontiguousarray(s2, dtype=np.int32)
@@ -127,9 +140,10 @@ class Plan:
         self.B = int(self.s1.size)
         h = ctypes.c_void_p()
         self.case4 = bool(case4)
-        self.jacobian = bool(jacobian)
+        self.jacobian = jacobian_mode(jacobian)
         opts = (_lib.PLAN_CASE4 if case4 else 0) | (0 if fuse else _lib.PLAN_NO_FUSE) | (
-            _lib.PLAN_SUSPEND if suspend else 0) | (_lib.PLAN_JACOBIAN if jacobian else 0)
+            _lib.PLAN_SUSPEND if suspend else 0) | (_lib.PLAN_JACOBIAN if self.jacobian else 0) | (
+            _lib.PLAN_JACOBIAN_STREAM if self.jacobian == "stream" else 0)
         _lib.check(lib.dcol_plan_create_ex(table.handle, self.B, _np_ptr(self.s1), _np_ptr(self.s2),
                                            opts, ctypes.byref(h)), "dcol_plan_create_ex")
         self.handle = h
@@ -334,7 +348,7 @@ class Engine:
         s2 = np.ascontiguousarray(s2, dtype=np.int32)
         if not cache or suspend:   # suspend plans own scratch: never shared through the cache
             return Plan(self.table, s1, s2, case4, fuse, suspend, jacobian)
-        key = (s1.tobytes(), s2.tobytes(), bool(case4), bool(fuse), bool(jacobian))
+        key = (s1.tobytes(), s2.tobytes(), bool(case4), bool(fuse), jacobian_mode(jacobian))
         with self._lock:
             p = self._plans.get(key)
             if p is None or p.table is not self.table:
@@ -351,13 +365,18 @@ class Engine:
                    contact=True, case4=False, jacobian=False) -> Result:
         """Host arrays in/out: s1, s2 int [B]; pose1, pose2 float64 [B, 6] (r, p).
         case4=True: the DCOL_CASE4 extension (see Plan).  jacobian=True: also Result.jac,
-        (B, 4, 12), the contact-point Jacobian (dcol_prox_jacobian_host)."""
+        (B, 4, 12), the contact-point Jacobian (dcol_prox_jacobian_host); pairs above 128
+        orthant rows are TOO_LARGE then.  jacobian="stream": with DCOL_JACOBIAN_STREAM, pairs
+        of 129 to 1,024 rows get their Jacobian from the streamed-row kernels."""
         s1 = np.ascontiguousarray(s1, dtype=np.int32).reshape(-1)
         s2 = np.ascontiguousarray(s2, dtype=np.int32).reshape(-1)
         B = s1.size
         p1 = np.ascontiguousarray(pose1, dtype=np.float64).reshape(B, 6)
         p2 = np.ascontiguousarray(pose2, dtype=np.float64).reshape(B, 6)
         flags = grad_flag(grad) | (_lib.CONTACT if contact else 0) | (_lib.CASE4 if case4 else 0)
+        jacobian = jacobian_mode(jacobian)
+        if jacobian == "stream":
+            flags |= _lib.JACOBIAN_STREAM
         alpha = np.empty(B)
         cp = np.empty((B, 3)) if contact else None
         g = np.empty((B, 12)) if flags & _lib.GRAD_ANY else None

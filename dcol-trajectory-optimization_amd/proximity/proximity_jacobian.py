@@ -15,10 +15,13 @@ from dcol_amd.engine import DEFAULT_TOL, default_engine, raise_for_status
 from dcol_amd.shapes import pose_of
 
 
-def proximity_jacobian(prim1, prim2, pdip_tol=DEFAULT_TOL, verbose=False):
+def proximity_jacobian(prim1, prim2, pdip_tol=DEFAULT_TOL, verbose=False, stream=False):
     """-> (alpha: float64, contact_point: ndarray(3), J: ndarray(4, 12)).  Raises like
     proximity_mrp / proximity_gradient.  J is NaN where the linearised KKT system at the
-    iterate is singular (the pair's status stays OK: alpha and the contact point are valid)."""
+    iterate is singular (the pair's status stays OK: alpha and the contact point are valid).
+    stream=True: a pair of 129 to 1,024 orthant rows (a many-faced polytope) gets its Jacobian
+    from the streamed-row kernels (Engine.solve_host(jacobian="stream")) instead of the
+    ValueError the default raises for it."""
     eng = default_engine()
     with eng._lock:
         s1 = eng.register_object(prim1)
@@ -26,6 +29,6 @@ def proximity_jacobian(prim1, prim2, pdip_tol=DEFAULT_TOL, verbose=False):
     p1 = np.reshape(pose_of(prim1), (1, 6))
     p2 = np.reshape(pose_of(prim2), (1, 6))
     res = eng.solve_host([s1], [s2], p1, p2, tol=pdip_tol, max_iter=eng.max_iter, grad=None, contact=True,
-                         jacobian=True)
+                         jacobian="stream" if stream else True)
     raise_for_status(int(res.status[0]))
     return res.alpha[0], res.contact[0].copy(), res.jac[0].copy()

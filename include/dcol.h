@@ -44,7 +44,10 @@ extern "C" {
                                    dcol_table_stop_pair_server, dcol_table_pair_server_running,
                                    dcol_debug_pair_stamps;
                                 5: the contact-point Jacobian: DCOL_PLAN_JACOBIAN, DCOL_JACOBIAN,
-                                   dcol_plan_run_jac, dcol_prox_jacobian_host */
+                                   dcol_plan_run_jac, dcol_prox_jacobian_host
+                                   (additive since, same number: DCOL_MAX_PAIR_ROWS;
+                                   DCOL_PLAN_JACOBIAN_STREAM, DCOL_JACOBIAN_STREAM -- a library
+                                   from before them answers DCOL_ERR_ARG "unknown option bits") */
 
 /* Primitive types (misc_primitive_constructor.py:4-88). */
 enum dcol_shape_type {
@@ -65,7 +68,10 @@ enum dcol_status {
     DCOL_NONFINITE = 4,   /* a non-finite value reached a factorisation                   */
     DCOL_TOO_LARGE = 5    /* more orthant rows than the engine's row capacity: DCOL_MAX_PAIR_ROWS
                              for a pair of combine cases 1-3; 32 for a case-4 pair (DCOL_PLAN_CASE4);
-                             128 in a DCOL_PLAN_JACOBIAN plan and dcol_prox_jacobian_host          */
+                             128 in a DCOL_PLAN_JACOBIAN plan and dcol_prox_jacobian_host, unless
+                             they opt into the streamed Jacobian copies
+                             (DCOL_PLAN_JACOBIAN_STREAM / DCOL_JACOBIAN_STREAM): then
+                             DCOL_MAX_PAIR_ROWS for cases 1-3 there too                          */
 };
 
 /* Orthant rows a pair's two primitives may bring together (polytope faces, polygon edges, the
@@ -95,10 +101,15 @@ enum dcol_flags {
                                dcol_comm_all_gather (e.g. on a stream of its own, so the
                                next step's solve overlaps it), or time the step without
                                its collective (comm = step - this, like for like)         */
-    DCOL_JACOBIAN = 64      /* dcol_plan_run_jac / dcol_prox_jacobian_host only: write the
+    DCOL_JACOBIAN = 64,     /* dcol_plan_run_jac / dcol_prox_jacobian_host only: write the
                                contact-point Jacobian d[x0,x1,x2,alpha] / d[r1,p1,r2,p2]
                                (DifferentiableCollisions.jl proximity_jacobian; see
                                dcol_plan_run_jac).  Independent of the gradient flags.      */
+    DCOL_JACOBIAN_STREAM = 128 /* dcol_prox_jacobian_host only (as DCOL_CASE4 is for the batch
+                               host call): the transient plan is made with
+                               DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM, so pairs of 129
+                               to DCOL_MAX_PAIR_ROWS rows get their Jacobian instead of
+                               DCOL_TOO_LARGE.  Without it the call is unchanged.            */
 };
 #define DCOL_GRAD_ANY (DCOL_GRAD_FD | DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)
 
@@ -120,12 +131,25 @@ enum dcol_plan_options {
                            its slowest pair converges; results are bitwise the same.  The plan
                            then owns device scratch written by every run: do not run it on
                            two streams at once (one plan per stream).                       */
-    DCOL_PLAN_JACOBIAN = 8 /* the plan can run dcol_plan_run_jac with DCOL_JACOBIAN: its pairs
+    DCOL_PLAN_JACOBIAN = 8, /* the plan can run dcol_plan_run_jac with DCOL_JACOBIAN: its pairs
                            are bucketed on the dense-row kernels (as under DCOL_NO_BALL / NO_CONE /
                            NO_PART / NO_BOX), each bucket at its shape's first lane count, and
                            it always takes the DCOL_FORM_BUCKETS form -- no fused or packed
                            launch, no suspend / resume, no order hint.  Not with
-                           DCOL_PLAN_SUSPEND (DCOL_ERR_ARG).                                */
+                           DCOL_PLAN_SUSPEND (DCOL_ERR_ARG).  Pairs above 128 rows get
+                           DCOL_TOO_LARGE unless DCOL_PLAN_JACOBIAN_STREAM is set too.      */
+    DCOL_PLAN_JACOBIAN_STREAM = 16 /* only together with DCOL_PLAN_JACOBIAN (alone: DCOL_ERR_ARG):
+                           pairs of combine cases 1-3 with 129 to DCOL_MAX_PAIR_ROWS orthant rows
+                           get a streamed bucket per (N, NSOC), as in a plain plan (one wave per
+                           slot, slots in descending row count), and dcol_plan_run_jac with
+                           DCOL_JACOBIAN writes their 48 entries from the streamed kernels'
+                           Jacobian copies; a run without DCOL_JACOBIAN launches the plain
+                           streamed kernels.  Either way alpha, contact, grad, iters and status
+                           of those pairs are bitwise what a plain plan returns.  Pairs of at
+                           most 128 rows keep their dense Jacobian bucket; pairs above
+                           DCOL_MAX_PAIR_ROWS rows and case-4 pairs above 32 keep
+                           DCOL_TOO_LARGE.  The Jacobian phase adds about six passes over the
+                           rows to a solve of about five per iteration. */
 };
 
 /* Return codes of every entry point. */
@@ -245,7 +269,10 @@ int dcol_plan_run(const dcol_plan* plan, const double* pose1, const double* pose
  * Where the contact point is not unique (face-to-face boxes) H is near-singular and the
  * entries are large and meaningless, as the derivative itself is.
  * The plan must have been made with DCOL_PLAN_JACOBIAN, and jac must not be NULL: else
- * DCOL_ERR_ARG (message in dcol_last_error).  The gradient flags are independent: grad is
+ * DCOL_ERR_ARG (message in dcol_last_error).  Pairs above 128 orthant rows have
+ * DCOL_TOO_LARGE (and NaN) in such a plan unless it was also made with
+ * DCOL_PLAN_JACOBIAN_STREAM; then pairs of cases 1-3 up to DCOL_MAX_PAIR_ROWS rows run the
+ * streamed-row kernels' Jacobian copies, under the same two NaN rules.  The gradient flags are independent: grad is
  * written in whichever mode is asked.  Without DCOL_JACOBIAN the call is dcol_plan_run (jac
  * ignored).  Asynchronous, capturable and allocation-free like dcol_plan_run.            */
 int dcol_plan_run_jac(const dcol_plan* plan, const double* pose1, const double* pose2, double tol,
@@ -253,7 +280,9 @@ int dcol_plan_run_jac(const dcol_plan* plan, const double* pose1, const double* 
                       double* jac, int32_t* iters, int32_t* status, void* stream);
 /* Host form of the same: HOST array-of-structures arrays in and out like
  * dcol_prox_batch_host, jac B x 4 x 12 (required); DCOL_JACOBIAN is implied.  Builds a
- * transient DCOL_PLAN_JACOBIAN plan (with DCOL_CASE4 in flags: plus DCOL_PLAN_CASE4).
+ * transient DCOL_PLAN_JACOBIAN plan (with DCOL_CASE4 in flags: plus DCOL_PLAN_CASE4; with
+ * DCOL_JACOBIAN_STREAM: plus DCOL_PLAN_JACOBIAN_STREAM, without which pairs above 128 rows
+ * get DCOL_TOO_LARGE).
  * Synchronous; calls on one table are serialised.                                         */
 int dcol_prox_jacobian_host(const dcol_table* table, int64_t B, const int32_t* shape1,
                             const int32_t* shape2, const double* pose1, const double* pose2,

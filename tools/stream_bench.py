@@ -10,7 +10,12 @@ minimum and median over --rounds rounds that alternate the batches.  Per batch o
 line: ms per step, pair-solves/s, mean iterations, ns per pair x row x iteration.  The first
 64 pairs of each batch are checked against the NumPy oracle (status, iteration counts, alpha
 1e-6 relative).
-Usage: python3 tools/stream_bench.py [--pairs 4096] [--steps 30] [--rounds 4]
+--jacobian: instead, the cost of the contact-point Jacobian on streamed pairs
+(csrc/dcol_kernels_stream_jac.hip): batches at 129, 256 and 1,024 rows for (4, 0) and at 256
+rows for (6, 1), each in ONE plan made with jacobian="stream"; per round the FD-only run (the
+plain streamed kernels) and the run with the Jacobian (their JAC copies, FD gradient too)
+alternate.  Per batch one JSON line: ms per step of both and their ratio (of the minima).
+Usage: python3 tools/stream_bench.py [--pairs 4096] [--steps 30] [--rounds 4] [--jacobian]
 """
 import argparse
 import json
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--check", type=int, default=64)
+    ap.add_argument("--jacobian", action="store_true")
     args = ap.parse_args()
     import torch
     from dcol_amd import Engine, ShapeSpec, alloc_outputs
@@ -57,6 +63,11 @@ def main():
     eng = Engine(device=0)
     dev = torch.device("cuda", 0)
     B = args.pairs
+    if args.jacobian:
+        jacobian_bench(args, eng, dev, rng, [("poly x poly 129", poly(65), poly(64)), ("poly x poly 256", poly(128), poly(128)),
+                                             ("poly x poly 1024", poly(512), poly(512)),
+                                             ("polygon x poly 256", gon(128), poly(128))])
+        return
     runs = []
     for name, a, b in cases:
         ia, ib = eng.register(a[0]), eng.register(b[0])
@@ -99,6 +110,52 @@ def main():
                           "ok": r["ok"], "mean_iters": round(r["iters"], 2), "ms_min": round(mn, 4), "ms_median": round(med, 4),
                           "pair_solves_per_s": round(B / (mn * 1e-3)),
                           "ns_per_pair_row_iter": round(mn * 1e6 / (B * rows * r["iters"]), 4)}), flush=True)
+
+
+def jacobian_bench(args, eng, dev, rng, cases):
+    import torch
+    from dcol_amd import alloc_outputs
+    B = args.pairs
+    runs = []
+    for name, a, b in cases:
+        ia, ib = eng.register(a[0]), eng.register(b[0])
+        p1 = np.hstack([rng.uniform(-3, 3, (B, 3)), rng.uniform(-1, 1, (B, 3))])
+        p2 = np.hstack([rng.uniform(-3, 3, (B, 3)), rng.uniform(-1, 1, (B, 3))])
+        runs.append(dict(name=name, rows=a[2] + b[2], ia=ia, ib=ib, p1=p1, p2=p2))
+    for r in runs:
+        plan = eng.plan(np.full(B, r["ia"], np.int32), np.full(B, r["ib"], np.int32), jacobian="stream")
+        d1 = torch.from_numpy(np.ascontiguousarray(r["p1"].T)).to(dev)
+        d2 = torch.from_numpy(np.ascontiguousarray(r["p2"].T)).to(dev)
+        out = alloc_outputs(B, dev, want_grad=True, want_contact=False, want_jac=True)
+        steps = {m: (lambda m=m, plan=plan, d1=d1, d2=d2, out=out: plan.run(d1, d2, grad="fd", contact=False, out=out,
+                                                                          jacobian=m == "jac")) for m in ("fd", "jac")}
+        for m in ("fd", "jac"):
+            for _ in range(3):
+                steps[m]()
+        torch.cuda.synchronize()
+        it, st = out["iters"].cpu().numpy(), out["status"].cpu().numpy()
+        fin = bool(np.isfinite(out["jac"].cpu().numpy()[:, st == 0]).all())
+        r.update(plan=plan, steps=steps, iters=float(it[st == 0].mean()), ok=int((st == 0).sum()), finite=fin,
+                 bucket=plan.buckets()[0], ms={"fd": [], "jac": []})
+    for _ in range(args.rounds):
+        for r in runs:
+            for m in ("fd", "jac"):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(args.steps):
+                    r["steps"][m]()
+                e1.record()
+                torch.cuda.synchronize()
+                r["ms"][m].append(e0.elapsed_time(e1) / args.steps)
+    for r in runs:
+        bk = r["bucket"]
+        fd, jac = float(np.min(r["ms"]["fd"])), float(np.min(r["ms"]["jac"]))
+        print(json.dumps({"batch": r["name"], "pairs": B, "rows": r["rows"], "bucket": [bk["N"], bk["nsoc"], bk["omax"], bk["lpp"]],
+                          "ok": r["ok"], "jac_finite": r["finite"], "mean_iters": round(r["iters"], 2),
+                          "ms_fd_min": round(fd, 4), "ms_fd_median": round(float(np.median(r["ms"]["fd"])), 4),
+                          "ms_jac_min": round(jac, 4), "ms_jac_median": round(float(np.median(r["ms"]["jac"])), 4),
+                          "jac_over_fd": round(jac / fd, 3)}), flush=True)
 
 
 if __name__ == "__main__":
