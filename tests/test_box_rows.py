@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import emul_lib
 from box_shapes import box_pairs, box_table
 from conftest import PKG, REPO, alpha_close, gpu_available, grad_close
 
@@ -35,19 +36,18 @@ def _check_vs_oracle(res, ref, rel_max):
 
 def test_emulated_box_rows_asymmetric_match_oracle(monkeypatch):
     from oracle import c_oracle
-    from test_emul_golden import emul
     rng = np.random.default_rng(11)
     tab, _ = box_table(rng)
     s1, s2, p1, p2 = box_pairs(rng, tab, 3000)
     d = dict(tab, s1=s1, s2=s2, pose1=p1, pose2=p2)
     monkeypatch.delenv("DCOL_NO_BOX", raising=False)
-    al, _, gr, it, st = emul(d, 1e-6, 1 | 4)
+    al, _, gr, it, st = emul_lib.solve(d, 1 | 4, tol=1e-6)
     ref = c_oracle.run_batch(tab, s1, s2, p1, p2, want_grad=True, threads=8)
     box = {"alpha": al, "grad": gr, "iters": it, "status": st}
     _check_vs_oracle(box, ref, 1e-9)
     # the same pairs on the dense rows: same iterations, rounding-level alpha
     monkeypatch.setenv("DCOL_NO_BOX", "1")
-    al2, _, gr2, it2, st2 = emul(d, 1e-6, 1 | 4)
+    al2, _, gr2, it2, st2 = emul_lib.solve(d, 1 | 4, tol=1e-6)
     np.testing.assert_array_equal(st2, st)
     np.testing.assert_array_equal(it2, it)
     ok = st == 0

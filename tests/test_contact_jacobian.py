@@ -6,7 +6,7 @@ Three layers, each checked against the one before:
   truth        central differences of x*[0:4] solved to mu < 1e-11 (the oracle's PDIP);
   restatement  tests/contact_jacobian_ref.py: the exact-complementarity linearisation at the
                returned iterate, on the oracle's own pieces (NumPy, pivoted solve);
-  kernel       the JAC copies of the HIP solver, emulated on x86 (tests/emul_jac) and on the GPU.
+  kernel       the JAC copies of the HIP solver, emulated on x86 (tests/emul) and on the GPU.
 
 Pairs are sampled as test_implicit_grad._pairs does (status-0 pairs, np.linspace indices);
 sc = max(|ref|_inf over the 4 x 12, 1).  scene_piano is left out of the truth comparison (its
@@ -37,52 +37,22 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import PKG, REPO, alpha_close, golden_files, load_golden
+import emul_lib
+from conftest import PKG, REPO, alpha_close
 from contact_jacobian_ref import contact_jacobian, tolerance
+from jacobian_cases import golden_set, iterate, registered, restated, sample_pairs
 
-GOLD = {p.split("/")[-1][:-4]: p for p in golden_files()}
 SETS = ["scene_quad", "scene_cone", "synthetic_mixed", "synthetic_polypoly", "large_polytopes"]
-EMUL_DIR = os.path.join(REPO, "tests", "emul_jac")
-EMUL_LIB = os.path.join(EMUL_DIR, "libdcol_emul_jac.so")
 HEADER = os.path.join(REPO, "include", "dcol.h")
 COND_MAX = 1e10
 EXCUSED_MAX = 3
-
-
-@functools.lru_cache(maxsize=None)
-def _golden(name):
-    return load_golden(GOLD[name])
-
-
-def _pairs(name, n):
-    d = _golden(name)
-    ok = np.flatnonzero(d["status"] == 0)
-    return d, ok[np.linspace(0, ok.size - 1, n).astype(int)]
-
-
-def _iterate(d, i, tol=None, case4=False):
-    from oracle import dcol_oracle as O
-    a, b = O.shape_from_table(d, d["s1"][i]), O.shape_from_table(d, d["s2"][i])
-    p1, p2 = d["pose1"][i], d["pose2"][i]
-    tol = float(d["tol"]) if tol is None else tol
-    _, _, x, s, z, _, dims = O.proximity(a, p1[:3], p1[3:], b, p2[:3], p2[3:], tol, case4)
-    return O, a, b, x, s, z, np.concatenate([p1, p2]), dims
-
-
-@functools.lru_cache(maxsize=None)
-def _restated(name, i, case4=False):
-    """(J, cond(H), tolerance) of pair i of a golden set: computed once, shared by the tests"""
-    O, a, b, x, s, z, th, dims = _iterate(_golden(name), i, case4=case4)
-    J, cond = contact_jacobian(O, a, b, x, s, z, th, dims, case4)
-    J.setflags(write=False)
-    return J, cond, tolerance(O, a, b, x, s, z, th, dims, J, case4)
 
 
 def _check_against_restatement(name, idx, jac):
     """The rule of the module docstring for the pairs idx of a set and their kernel results"""
     excused = []
     for j, i in enumerate(idx):
-        J, cond, tol = _restated(name, int(i))
+        J, cond, tol = restated(name, int(i))
         err = np.abs(jac[j] - J).max()
         sc = max(np.abs(J).max(), 1.0)
         print(f"{name}[{i}]: err {err / sc:.2e} tol {tol / sc:.2e} cond(H) {cond:.1e}")
@@ -123,16 +93,16 @@ def test_restatement_matches_true_derivative(name):
       synthetic_mixed     0   1.2e-3   2.8e+0
       synthetic_polypoly  0   2.1e-5   2.1e-5   (orthant rows only: the two forms coincide)
       large_polytopes     0   2.2e-3   1.8e+0"""
-    d, idx = _pairs(name, 24)
+    d, idx = sample_pairs(name, 24)
     ill, worst, worst_nt = [], 0.0, 0.0
     for i in idx:
-        O, a, b, x, s, z, th, dims = _iterate(d, i)
+        O, a, b, x, s, z, th, dims = iterate(d, i)
         T, T3 = _truth(O, a, b, th, 1e-5), _truth(O, a, b, th, 3e-5)
         sc = max(np.abs(T).max(), 1.0)
         if not np.abs(T - T3).max() <= 1e-4 * sc:
             ill.append(int(i))
             continue
-        J, _, _ = _restated(name, int(i))
+        J, _, _ = restated(name, int(i))
         Jn, _ = contact_jacobian(O, a, b, x, s, z, th, dims, nt=True)
         err, err_nt = np.abs(J - T).max() / sc, np.abs(Jn - T).max() / sc
         worst, worst_nt = max(worst, err), max(worst_nt, err_nt)
@@ -143,33 +113,13 @@ def test_restatement_matches_true_derivative(name):
 
 def emul_jac(d, idx, flags=4, max_iter=50, case4=False):
     """Pairs idx of a golden-layout table through the x86 build of the JAC copies"""
-    from dcol_amd import make_descs, spec_from_arrays
-    if not os.path.exists(EMUL_LIB):   # (build() makes it; a bare checkout builds it here)
-        subprocess.run(["make", "-C", EMUL_DIR, "-j8", "-s"], check=True)
-    lib = ctypes.CDLL(EMUL_LIB)
-    P = ctypes.c_void_p
-    specs = [spec_from_arrays(d, k) for k in range(len(d["type"]))]
-    descs, keep = make_descs(specs)
-    B = len(idx)
-    s1 = np.ascontiguousarray(d["s1"][idx], np.int32)
-    s2 = np.ascontiguousarray(d["s2"][idx], np.int32)
-    p1 = np.ascontiguousarray(d["pose1"][idx])
-    p2 = np.ascontiguousarray(d["pose2"][idx])
-    al, ct, gr, jc = np.empty(B), np.empty((B, 3)), np.empty((B, 12)), np.empty((B, 4, 12))
-    it, st = np.empty(B, np.int32), np.empty(B, np.int32)
-    rc = lib.dcol_emul_jac_batch(descs, ctypes.c_int32(len(specs)), ctypes.c_int64(B), P(s1.ctypes.data),
-                                 P(s2.ctypes.data), P(p1.ctypes.data), P(p2.ctypes.data), ctypes.c_double(float(d["tol"])),
-                                 ctypes.c_int32(max_iter), ctypes.c_int32(flags), ctypes.c_int32(int(case4)),
-                                 P(al.ctypes.data), P(ct.ctypes.data), P(gr.ctypes.data), P(jc.ctypes.data),
-                                 P(it.ctypes.data), P(st.ctypes.data))
-    assert rc == 0
-    del keep
+    al, ct, gr, jc, it, st = emul_lib.solve(d, flags, idx, max_iter=max_iter, instance="jac", case4=case4)
     return al, ct, jc, it, st
 
 
 @functools.lru_cache(maxsize=None)
 def _emulated(name):
-    d, idx = _pairs(name, 40)
+    d, idx = sample_pairs(name, 40)
     return idx, emul_jac(d, idx)
 
 
@@ -178,7 +128,7 @@ def test_emulated_kernel_matches_restatement(name):
     """The kernel's Jacobian phase (x86 build, one lane per pair) against the restatement at
     the same 40 pairs per set, under the rule of the module docstring."""
     idx, (al, ct, jc, it, st) = _emulated(name)
-    d = _golden(name)
+    d = golden_set(name)
     assert np.all(st == 0)
     np.testing.assert_array_equal(it, d["iters"][idx])
     assert np.all(alpha_close(al, d["alpha"][idx]))
@@ -192,12 +142,12 @@ def test_alpha_row_matches_reference_gradient(name):
     """Row 3 of J is d alpha / d pose: within 5e-3 sc of the golden FD gradient where
     alpha > 1e-2 (the bound test_gpu_implicit_matches_oracle uses for the implicit mode)."""
     idx, (al, ct, jc, it, st) = _emulated(name)
-    d = _golden(name)
+    d = golden_set(name)
     n = 0
     for j, i in enumerate(idx):
         if not d["alpha"][i] > 1e-2:
             continue
-        J, _, _ = _restated(name, int(i))
+        J, _, _ = restated(name, int(i))
         sc = max(np.abs(J).max(), 1.0)
         assert np.abs(jc[j, 3] - d["grad"][i]).max() <= 5e-3 * sc, (name, i)
         n += 1
@@ -206,7 +156,7 @@ def test_alpha_row_matches_reference_gradient(name):
 
 def test_emulated_failure_rows_are_nan():
     """A pair that does not converge gets NaN in all 48 entries (edge_cases at max_iter 3)."""
-    d, idx = _pairs("edge_cases", 12)
+    d, idx = sample_pairs("edge_cases", 12)
     al, ct, jc, it, st = emul_jac(d, idx, max_iter=3)
     assert np.all(st == 1) and np.all(it == 3)
     assert np.all(np.isnan(jc)) and np.all(np.isnan(al))
@@ -232,9 +182,9 @@ def test_header_exports_and_binding_agree():
     assert int(re.search(r"\bDCOL_JACOBIAN\s*=\s*(\d+)", txt).group(1)) == _lib.JACOBIAN == 64
     assert int(re.search(r"\bDCOL_PLAN_JACOBIAN\s*=\s*(\d+)", txt).group(1)) == _lib.PLAN_JACOBIAN == 8
     assert int(re.search(r"#define\s+DCOL_ABI_VERSION\s+(\d+)", txt).group(1)) == _lib.ABI_VERSION == 5
-    if not os.path.exists(EMUL_LIB):
-        subprocess.run(["make", "-C", EMUL_DIR, "-j8", "-s"], check=True)
-    assert hasattr(ctypes.CDLL(EMUL_LIB), "dcol_emul_jac_batch")
+    # the emulator's JAC instance: one pair through it (emul_lib raises on an error return)
+    jc = emul_jac(*sample_pairs("scene_quad", 1))[2]
+    assert jc.shape == (1, 4, 12) and np.all(np.isfinite(jc))
     # argument checks that need no device: a NULL plan
     assert lib.dcol_plan_run_jac(None, None, None, 1e-6, 50, _lib.JACOBIAN, None, None, None, None, None, None,
                                  None) == _lib.ERR_ARG
@@ -261,20 +211,6 @@ def test_jac_variant_list():
 # ---------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------
-_IDS = {}
-
-
-def _register(engine, d):
-    """engine shape ids of a golden table's pairs (registered once per engine and table)"""
-    from dcol_amd import spec_from_arrays
-    key = (id(engine), id(d))
-    if key not in _IDS:
-        _IDS[key] = (engine, d, np.array([engine.register(spec_from_arrays(d, k)) for k in range(len(d["type"]))],
-                                         dtype=np.int32))
-    ids = _IDS[key][2]
-    return ids[d["s1"]], ids[d["s2"]]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SETS)
 def test_gpu_jacobian_matches_restatement(engine, name):
@@ -282,8 +218,8 @@ def test_gpu_jacobian_matches_restatement(engine, name):
     rule of the module docstring); in the same run alpha, contact, iters and status meet the
     parity tolerances against the golden values, and the FD gradient is still written."""
     from conftest import grad_close
-    d, idx = _pairs(name, 48)
-    s1, s2 = _register(engine, d)
+    d, idx = sample_pairs(name, 48)
+    s1, s2 = registered(engine, d)
     res = engine.solve_host(s1[idx], s2[idx], d["pose1"][idx], d["pose2"][idx], tol=float(d["tol"]), grad="fd",
                             jacobian=True)
     assert res.jac.shape == (48, 4, 12)
@@ -301,7 +237,7 @@ def _mixed_selection(n_mixed, n_large):
     out = []
     for name, n in (("synthetic_mixed", n_mixed), ("large_polytopes", n_large)):
         if n:
-            out += [(name, int(i)) for i in _pairs(name, n)[1]]
+            out += [(name, int(i)) for i in sample_pairs(name, n)[1]]
     return out
 
 
@@ -311,8 +247,8 @@ def _run_guarded(engine, sel):
     import torch
     s1, s2, p1, p2 = [], [], [], []
     for name, i in sel:
-        d = _golden(name)
-        a, b = _register(engine, d)
+        d = golden_set(name)
+        a, b = registered(engine, d)
         s1.append(a[i]); s2.append(b[i]); p1.append(d["pose1"][i]); p2.append(d["pose2"][i])
     B = len(sel)
     plan = engine.plan(np.array(s1, np.int32), np.array(s2, np.int32), cache=False, jacobian=True)
@@ -337,10 +273,10 @@ def _check_selection(sel, o, jac):
     assert np.all(o["status"] == 0)
     excused = {}
     for j, (name, i) in enumerate(sel):
-        d = _golden(name)
+        d = golden_set(name)
         assert o["iters"][j] == d["iters"][i]
         assert alpha_close(o["alpha"][j], d["alpha"][i])
-        J, cond, tol = _restated(name, i)
+        J, cond, tol = restated(name, i)
         sc = max(np.abs(J).max(), 1.0)
         err = np.abs(jac[j] - J).max()
         print(f"{name}[{i}]: err {err / sc:.2e} tol {tol / sc:.2e} cond(H) {cond:.1e}")
@@ -383,8 +319,8 @@ def test_gpu_partial_group_wave(engine):
     cands = _mixed_selection(0, 24)
     by_key = {}
     for name, i in cands:
-        d = _golden(name)
-        a, b = _register(engine, d)
+        d = golden_set(name)
+        a, b = registered(engine, d)
         bk = engine.plan([a[i]], [b[i]], cache=False, jacobian=True).buckets()[0]
         if bk["kind"] == "solve" and bk["lpp"] >= 4:
             by_key.setdefault((bk["N"], bk["nsoc"], bk["omax"], bk["lpp"]), []).append((name, i))
@@ -400,8 +336,8 @@ def test_gpu_failure_rows(engine):
     """edge_cases.  At max_iter = 3 every solvable pair has status MAXITER (the unsupported
     pairs keep UNSUPPORTED) and all 48 entries of every pair are NaN.  At the default settings
     the pairs with a non-zero status have NaN rows and the others finite rows."""
-    d = _golden("edge_cases")
-    s1, s2 = _register(engine, d)
+    d = golden_set("edge_cases")
+    s1, s2 = registered(engine, d)
     res = engine.solve_host(s1, s2, d["pose1"], d["pose2"], tol=float(d["tol"]), max_iter=3, grad=None, jacobian=True)
     np.testing.assert_array_equal(res.status, np.where(d["status"] == 2, 2, 1))
     assert np.all(np.isnan(res.jac))
@@ -417,7 +353,8 @@ def test_gpu_case4_pair(engine):
     """A case-4 pair (capsule x polygon, N = 7) with case4=True, jacobian=True against the
     restatement called with case4=True."""
     from oracle import dcol_oracle as O
-    from test_case4 import CAPSULE, POLYGON, case4_table
+    from case4_shapes import case4_table
+    from geometry_bruteforce import CAPSULE, POLYGON
     tab = case4_table(np.random.default_rng(5))
     k1 = int(np.flatnonzero(tab["type"] == CAPSULE)[0])
     k2 = int(np.flatnonzero(tab["type"] == POLYGON)[0])
@@ -444,11 +381,11 @@ def test_gpu_dropin_equals_batch_bitwise(engine, name):
     """proximity_jacobian on one pair equals the batch result bitwise (alpha, contact, J)."""
     from dcol_amd import default_engine
     from proximity.proximity_jacobian import proximity_jacobian
-    from test_dropin import objects_from_golden, pose_pair
-    d, idx = _pairs(name, 48)
+    from dropin_objects import objects_from_golden, pose_pair
+    d, idx = sample_pairs(name, 48)
     i = int(idx[17])
     eng = default_engine()
-    s1, s2 = _register(eng, d)
+    s1, s2 = registered(eng, d)
     res = eng.solve_host(s1[idx], s2[idx], d["pose1"][idx], d["pose2"][idx], tol=float(d["tol"]), grad=None,
                          jacobian=True)
     a, b = pose_pair(objects_from_golden(d), d, i)
@@ -467,8 +404,8 @@ def test_gpu_run_jac_argument_errors(engine):
     import torch
     from dcol_amd import _lib
     from dcol_amd.engine import Plan, alloc_outputs
-    d, idx = _pairs("scene_quad", 8)
-    s1, s2 = _register(engine, d)
+    d, idx = sample_pairs("scene_quad", 8)
+    s1, s2 = registered(engine, d)
     dev = torch.device("cuda", engine.device)
     t1 = torch.tensor(np.ascontiguousarray(d["pose1"][idx].T), device=dev)
     t2 = torch.tensor(np.ascontiguousarray(d["pose2"][idx].T), device=dev)

@@ -1,37 +1,12 @@
 """x86 build of the device solver (tests/emul, LPP = 1) against the reference's golden
 vectors -- checks the kernel's arithmetic without a GPU.  The emulator is built by build()
 (__graft_entry__.py) or, when missing, by tests/conftest.py (`make -C tests/emul -j8`,
-~3.5 min of hipcc host compilation, one object per (N, NSOC) and row form)."""
-import ctypes
-import os
-
+minutes of hipcc host compilation, one object per (N, NSOC) and row form)."""
 import numpy as np
 import pytest
 
-from conftest import REPO, alpha_close, golden_files, grad_close, load_golden
-
-LIB = os.path.join(REPO, "tests", "emul", "libdcol_emul.so")
-
-
-def emul(d, tol, flags, max_iter=50):
-    from dcol_amd import make_descs, spec_from_arrays
-    lib = ctypes.CDLL(LIB)
-    P = ctypes.c_void_p
-    specs = [spec_from_arrays(d, k) for k in range(len(d["type"]))]
-    descs, keep = make_descs(specs)
-    B = len(d["s1"])
-    s1 = np.ascontiguousarray(d["s1"], np.int32)
-    s2 = np.ascontiguousarray(d["s2"], np.int32)
-    p1 = np.ascontiguousarray(d["pose1"])
-    p2 = np.ascontiguousarray(d["pose2"])
-    al, ct, gr = np.empty(B), np.empty((B, 3)), np.empty((B, 12))
-    it, st = np.empty(B, np.int32), np.empty(B, np.int32)
-    rc = lib.dcol_emul_batch(descs, ctypes.c_int32(len(specs)), ctypes.c_int64(B), P(s1.ctypes.data),
-                             P(s2.ctypes.data), P(p1.ctypes.data), P(p2.ctypes.data), ctypes.c_double(tol),
-                             ctypes.c_int32(max_iter), ctypes.c_int32(flags), P(al.ctypes.data), P(ct.ctypes.data),
-                             P(gr.ctypes.data), P(it.ctypes.data), P(st.ctypes.data))
-    assert rc == 0
-    return al, ct, gr, it, st
+import emul_lib
+from conftest import alpha_close, golden_files, grad_close, load_golden
 
 
 @pytest.mark.parametrize("orth_rows", ["partitioned", "dense"])
@@ -53,7 +28,7 @@ def test_emulated_kernel_matches_reference(path, flags, soc_rows, orth_rows, mon
     else:
         monkeypatch.delenv("DCOL_NO_PART", raising=False)
     d = load_golden(path)
-    al, ct, gr, it, st = emul(d, float(d["tol"]), flags)
+    al, ct, gr, it, st = emul_lib.solve(d, flags)
     np.testing.assert_array_equal(st, d["status"])
     ok = d["status"] == 0
     np.testing.assert_array_equal(it[ok], d["iters"][ok])

@@ -2,12 +2,11 @@
 hint_wave_slot, dcol_capi.cpp plan_hints): it only changes which lane group of which wave
 solves which pair.
 
-CPU: the permutation rule in its scalar form (tests/emul_hint), on random bytes.
+CPU: the permutation rule in its scalar form (tests/emul), on random bytes.
 GPU: tests/order_hint_child.py runs the same scenarios in two fresh processes, with the
 hint and under DCOL_NO_ORDER_HINT=1; every output of every run must be bitwise equal, no
 prefilled sentinel may survive (a slot nobody solved), and the runs at the golden poses must
 give the goldens' status and iteration counts."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -15,7 +14,8 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import REPO, golden_files, load_golden
+import emul_lib
+from conftest import golden_files, load_golden
 
 import order_hint_child as child
 
@@ -25,19 +25,7 @@ KEYS = ("alpha", "contact", "grad", "iters", "status")
 # ------------------------------------------------------------------ CPU: the rule
 @pytest.fixture(scope="module")
 def hint_order():
-    d = os.path.join(REPO, "tests", "emul_hint")
-    # (built by build(); a fresh checkout that ran no build() makes it here, like conftest's libraries)
-    subprocess.run(["make", "-C", d, "-s"], check=True)
-    lib = ctypes.CDLL(os.path.join(d, "libdcol_hint_emul.so"))
-    lib.dcol_emul_hint_order.restype = None
-    lib.dcol_emul_hint_order.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-
-    def order(h):
-        h = np.ascontiguousarray(h, np.uint8)
-        o = np.full(len(h), -1, np.int32)
-        lib.dcol_emul_hint_order(h.ctypes.data, len(h), o.ctypes.data)
-        return o
-    return order
+    return emul_lib.hint_order
 
 
 PPW = (64, 32, 16, 8)   # pairs per wave at 1, 2, 4, 8 lanes per pair

@@ -1,5 +1,5 @@
 """The plan policy (csrc/dcol_plan.hpp plan_layout: which kernel copy, lane count, launch form
-and stream each pair of a batch gets) through its x86 build (tests/emul_plan) -- no GPU.
+and stream each pair of a batch gets) through its x86 build (tests/emul) -- no GPU.
 
 * tests/plan_layouts.json (tools/record_plan_layouts.py: what the library's plans launched on
   the device, over the grid of tests/plan_cases.py) replays field for field.

@@ -5,14 +5,12 @@ DCOL_JACOBIAN_STREAM), on the CPU.
 Fixture tests/golden/huge/huge_rows.npz (tests/test_stream_rows.py); ok = its 144 pairs the
 reference solves.  Layers as in tests/test_contact_jacobian.py: the truth (central differences
 of the solution at mu < 1e-11), the NumPy restatement (tests/contact_jacobian_ref.py), the
-kernel's x86 build (tests/emul_stream_jac, one lane walking every row).
+kernel's x86 build (tests/emul, one lane walking every row).
 
 Kernel-against-restatement rule: err <= contact_jacobian_ref.tolerance(...) for EVERY compared
 pair, none excused.  (On the 144 pairs cond(H) <= 1.6e8, the tolerance lies between 1e-7 sc
 and 4.3e-7 sc, every J is finite, and a 1e-11 relative perturbation of (x, s, z) moves J by at
 most 0.008 of the tolerance: there is no near-singular pair to excuse.)"""
-import ctypes
-import functools
 import os
 import re
 import subprocess
@@ -20,136 +18,28 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import REPO, load_golden
-from contact_jacobian_ref import contact_jacobian, tolerance
-from test_stream_rows import HUGE, TOO_LARGE, UNSUPPORTED, _shape_set
-from test_stream_rows import LIB as PLAIN_LIB
-from test_stream_rows import DIR as PLAIN_DIR
+import emul_lib
+from conftest import REPO
+from stream_cases import (TOO_LARGE, UNSUPPORTED, bits, check_against_restatement, huge, iterate, ok_pairs, restated,
+                          plan, shape_set)
 
-DIR = os.path.join(REPO, "tests", "emul_stream_jac")
-LIB = os.path.join(DIR, "libdcol_stream_jac_emul.so")
 HEADER = os.path.join(REPO, "include", "dcol.h")
-P = ctypes.c_void_p
 FD, CONTACT, JACOBIAN = 1, 4, 64
 PLAN_CASE4, PLAN_JACOBIAN, PLAN_JACOBIAN_STREAM = 1, 8, 16
 
 
-@functools.lru_cache(maxsize=None)
-def huge():
-    return load_golden(HUGE)
+def emul_jac(idx, flags, max_iter=50):
+    return emul_lib.solve(huge(), flags, idx, max_iter=max_iter, instance="stream_jac")
 
 
-def ok_pairs():
-    d = huge()
-    return np.flatnonzero((d["expect_status"] == 0) & (d["status"] == 0))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(LIB):   # (build() makes it; a bare checkout builds it here)
-        subprocess.run(["make", "-C", DIR, "-s", "libdcol_stream_jac_emul.so"], check=True)
-    return ctypes.CDLL(LIB)
+def emul_plain(idx, flags, max_iter=50):
+    return emul_lib.solve(huge(), flags, idx, max_iter=max_iter, instance="stream")
 
 
 @pytest.fixture(scope="module")
-def plain_lib():
-    if not os.path.exists(PLAIN_LIB):
-        subprocess.run(["make", "-C", PLAIN_DIR, "-s", "libdcol_stream_emul.so"], check=True)
-    return ctypes.CDLL(PLAIN_LIB)
-
-
-def _iterate(i):
-    from oracle import dcol_oracle as O
-    d = huge()
-    a, b = O.shape_from_table(d, d["s1"][i]), O.shape_from_table(d, d["s2"][i])
-    p1, p2 = d["pose1"][i], d["pose2"][i]
-    _, _, x, s, z, _, dims = O.proximity(a, p1[:3], p1[3:], b, p2[:3], p2[3:], float(d["tol"]))
-    return O, a, b, x, s, z, np.concatenate([p1, p2]), dims
-
-
-@functools.lru_cache(maxsize=None)
-def restated(i):
-    """(J, cond(H), tolerance) of fixture pair i: computed once, shared by the tests (and by
-    tests/test_stream_jacobian_gpu.py), never modified"""
-    O, a, b, x, s, z, th, dims = _iterate(i)
-    J, cond = contact_jacobian(O, a, b, x, s, z, th, dims)
-    J.setflags(write=False)
-    return J, cond, tolerance(O, a, b, x, s, z, th, dims, J)
-
-
-def check_against_restatement(idx, jac):
-    """The module docstring's rule for the fixture pairs idx and their kernel results; every
-    figure is printed before the assertion"""
-    rows = huge()["rows"]
-    worst = (0.0, -1)
-    bad = []
-    for j, i in enumerate(idx):
-        J, cond, tol = restated(int(i))
-        sc = max(np.abs(J).max(), 1.0)
-        err = np.abs(jac[j] - J).max()
-        print(f"pair {int(i)} rows {int(rows[i])}: err {err / sc:.2e} tol {tol / sc:.2e} cond(H) {cond:.1e}")
-        if not err <= tol:     # (NaN fails)
-            bad.append((int(i), int(rows[i]), float(err / sc), float(tol / sc), float(cond)))
-        if np.isfinite(err) and err / tol > worst[0]:
-            worst = (float(err / tol), int(i))
-    print(f"worst err / tolerance {worst[0]:.3f} at pair {worst[1]}")
-    assert not bad, bad
-
-
-def _descs(d):
-    from dcol_amd import make_descs, spec_from_arrays
-    specs = [spec_from_arrays(d, k) for k in range(len(d["type"]))]
-    descs, keep = make_descs(specs)
-    return descs, keep, len(specs)
-
-
-def _inputs(d, idx):
-    return (np.ascontiguousarray(d["s1"][idx], np.int32), np.ascontiguousarray(d["s2"][idx], np.int32),
-            np.ascontiguousarray(d["pose1"][idx]), np.ascontiguousarray(d["pose2"][idx]))
-
-
-def emul_jac(lib, idx, flags, max_iter=50):
-    d = huge()
-    descs, keep, n = _descs(d)
-    B = len(idx)
-    s1, s2, p1, p2 = _inputs(d, idx)
-    al, ct, gr, jc = np.empty(B), np.empty((B, 3)), np.empty((B, 12)), np.full((B, 4, 12), -7.0)
-    it, st = np.empty(B, np.int32), np.empty(B, np.int32)
-    rc = lib.dcol_emul_stream_jac_batch(descs, ctypes.c_int32(n), ctypes.c_int64(B), P(s1.ctypes.data), P(s2.ctypes.data),
-                                        P(p1.ctypes.data), P(p2.ctypes.data), ctypes.c_double(float(d["tol"])),
-                                        ctypes.c_int32(max_iter), ctypes.c_int32(flags), P(al.ctypes.data),
-                                        P(ct.ctypes.data), P(gr.ctypes.data), P(jc.ctypes.data), P(it.ctypes.data),
-                                        P(st.ctypes.data))
-    assert rc == 0
-    del keep
-    return al, ct, gr, jc, it, st
-
-
-def emul_plain(lib, idx, flags, max_iter=50):
-    d = huge()
-    descs, keep, n = _descs(d)
-    B = len(idx)
-    s1, s2, p1, p2 = _inputs(d, idx)
-    al, ct, gr = np.empty(B), np.empty((B, 3)), np.empty((B, 12))
-    it, st = np.empty(B, np.int32), np.empty(B, np.int32)
-    rc = lib.dcol_emul_stream_batch(descs, ctypes.c_int32(n), ctypes.c_int64(B), P(s1.ctypes.data), P(s2.ctypes.data),
-                                    P(p1.ctypes.data), P(p2.ctypes.data), ctypes.c_double(float(d["tol"])),
-                                    ctypes.c_int32(max_iter), ctypes.c_int32(flags), P(al.ctypes.data), P(ct.ctypes.data),
-                                    P(gr.ctypes.data), P(it.ctypes.data), P(st.ctypes.data))
-    assert rc == 0
-    del keep
-    return al, ct, gr, it, st
-
-
-@pytest.fixture(scope="module")
-def jac_run(lib):
+def jac_run():
     """the x86 Jacobian copies on the 144 pairs, FD gradient + contact + Jacobian (shared, not modified)"""
-    return emul_jac(lib, ok_pairs(), FD | CONTACT | JACOBIAN)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
+    return emul_jac(ok_pairs(), FD | CONTACT | JACOBIAN)
 
 
 # ---------------------------------------------------------------- 1. the yardstick
@@ -183,7 +73,7 @@ def test_restatement_matches_true_derivative():
     idx = ok[np.linspace(0, ok.size - 1, 24).astype(int)]
     ill, worst = [], (0.0, -1)
     for i in idx:
-        O, a, b, x, s, z, th, dims = _iterate(int(i))
+        O, a, b, x, s, z, th, dims = iterate(huge(), int(i))
         T, T3 = _truth(O, a, b, th, 1e-5), _truth(O, a, b, th, 3e-5)
         sc = max(np.abs(T).max(), 1.0)
         if not np.abs(T - T3).max() <= 1e-4 * sc:
@@ -200,15 +90,15 @@ def test_restatement_matches_true_derivative():
 
 
 # ---------------------------------------------------------------- 2. the x86 Jacobian copies
-def test_emulated_kernel_matches_restatement(plain_lib, jac_run):
+def test_emulated_kernel_matches_restatement(jac_run):
     """All 144 pairs: status 0, the fixture's iteration counts; alpha, contact and grad bitwise
-    what the plain streamed build (tests/emul_stream) returns for the same pairs and flags; J
+    what the plain streamed instance returns for the same pairs and flags; J
     under the module docstring's rule."""
     d, ok = huge(), ok_pairs()
     al, ct, gr, jc, it, st = jac_run
     assert np.all(st == 0)
     np.testing.assert_array_equal(it, d["iters"][ok])
-    pal, pct, pgr, pit, pst = emul_plain(plain_lib, ok, FD | CONTACT)
+    pal, pct, pgr, pit, pst = emul_plain(ok, FD | CONTACT)
     np.testing.assert_array_equal(pst, st)
     np.testing.assert_array_equal(pit, it)
     for name, a, b in (("alpha", al, pal), ("contact", ct, pct), ("grad", gr, pgr)):
@@ -217,12 +107,12 @@ def test_emulated_kernel_matches_restatement(plain_lib, jac_run):
     check_against_restatement(ok, jc)
 
 
-def test_jacobian_without_gradient_is_the_same(lib, jac_run):
+def test_jacobian_without_gradient_is_the_same(jac_run):
     """Without a gradient flag the phase forms the z aggregates itself: the same J, bitwise."""
     ok = ok_pairs()
     idx = ok[np.linspace(0, ok.size - 1, 16).astype(int)]
     pos = np.searchsorted(ok, idx)
-    al, ct, gr, jc, it, st = emul_jac(lib, idx, CONTACT | JACOBIAN)
+    al, ct, gr, jc, it, st = emul_jac(idx, CONTACT | JACOBIAN)
     np.testing.assert_array_equal(bits(jc), bits(jac_run[3][pos]))
     np.testing.assert_array_equal(bits(al), bits(jac_run[0][pos]))
 
@@ -246,49 +136,29 @@ def test_alpha_row_matches_reference_gradient(jac_run):
 
 
 # ---------------------------------------------------------------- 4. failure rows
-def test_failure_rows_are_nan(lib):
+def test_failure_rows_are_nan():
     d, ok = huge(), ok_pairs()
     idx = ok[np.linspace(0, ok.size - 1, 12).astype(int)]
-    al, ct, gr, jc, it, st = emul_jac(lib, idx, FD | CONTACT | JACOBIAN, max_iter=3)
+    al, ct, gr, jc, it, st = emul_jac(idx, FD | CONTACT | JACOBIAN, max_iter=3)
     assert np.all(st == 1) and np.all(it == 3)
     assert np.all(np.isnan(jc)) and np.all(np.isnan(al))
     big = np.flatnonzero(d["expect_status"] == TOO_LARGE)
     c4 = np.flatnonzero(d["expect_status"] == UNSUPPORTED)
     assert big.size == 2 and set(d["rows"][big].tolist()) == {1025} and c4.size == 6
     idx = np.concatenate([big, c4])
-    al, ct, gr, jc, it, st = emul_jac(lib, idx, FD | CONTACT | JACOBIAN)
+    al, ct, gr, jc, it, st = emul_jac(idx, FD | CONTACT | JACOBIAN)
     np.testing.assert_array_equal(st, d["expect_status"][idx])
     assert np.all(np.isnan(jc)) and np.all(np.isnan(al)) and np.all(np.isnan(gr))
 
 
 # ---------------------------------------------------------------- 5. classify and plan
-def _plan(lib, descs, n, s1, s2, options=0, simds=256, expect_rc=0):
-    B = len(s1)
-    s1 = np.ascontiguousarray(s1, np.int32)
-    s2 = np.ascontiguousarray(s2, np.int32)
-    info = np.zeros((64, 10), np.int32)
-    pairs, slot0, rows = np.zeros(64, np.int64), np.zeros(64, np.int64), np.zeros(64, np.int64)
-    head, perm = np.zeros(2, np.int64), np.zeros(B, np.int32)
-    rc = lib.dcol_emul_stream_jac_plan(descs, ctypes.c_int32(n), ctypes.c_int32(simds), ctypes.c_int64(B),
-                                       P(s1.ctypes.data), P(s2.ctypes.data), ctypes.c_int32(options), ctypes.c_int32(64),
-                                       P(info.ctypes.data), P(pairs.ctypes.data), P(slot0.ctypes.data),
-                                       P(rows.ctypes.data), P(head.ctypes.data), P(perm.ctypes.data))
-    assert rc == expect_rc
-    if rc:
-        return None
-    cols = ("kind", "N", "nsoc", "omax", "lpp", "oe", "flags", "code", "stream", "lane")
-    buckets = [dict(zip(cols, info[i].tolist()), pairs=int(pairs[i]), slot0=int(slot0[i]), rows=int(rows[i]))
-               for i in range(int(head[0]))]
-    return buckets, int(head[1]), perm
-
-
-def test_plan_with_streamed_jacobian_bucket(lib):
-    descs, keep, n, k = _shape_set()
+def test_plan_with_streamed_jacobian_bucket():
+    descs, keep, n, k = shape_set()
     JS = PLAN_JACOBIAN | PLAN_JACOBIAN_STREAM
     pairs = [(k[123], k[6]), (k[512], k[512]), (k[6], k[6]), (k[122], k[6])]
     nrow = {k[6]: 6, k[122]: 122, k[123]: 123, k[512]: 512}
     s1, s2 = [p[0] for p in pairs], [p[1] for p in pairs]
-    b, form, perm = _plan(lib, descs, n, s1, s2, JS)
+    b, form, perm = plan(descs, n, s1, s2, JS)
     assert form == 0                                           # DCOL_FORM_BUCKETS
     assert not any(x["kind"] == 1 for x in b)
     st = [x for x in b if x["stream"]]
@@ -299,29 +169,29 @@ def test_plan_with_streamed_jacobian_bucket(lib):
     assert st[0]["rows"] == 1024 + 192
     assert sorted(perm.tolist()) == [0, 1, 2, 3]
     # the register buckets: those of option 8 on the two small pairs alone
-    b0, form0, _ = _plan(lib, descs, n, s1[2:], s2[2:], PLAN_JACOBIAN)
+    b0, form0, _ = plan(descs, n, s1[2:], s2[2:], PLAN_JACOBIAN)
     key = lambda x: (x["kind"], x["N"], x["nsoc"], x["omax"], x["lpp"], x["oe"], x["flags"], x["pairs"])  # noqa: E731
     assert form0 == 0 and sorted(key(x) for x in b if not x["stream"]) == sorted(key(x) for x in b0)
     assert all(x["omax"] <= 128 for x in b0)
     # without option 16 the same plan keeps today's behaviour
-    b8, _, _ = _plan(lib, descs, n, s1, s2, PLAN_JACOBIAN)
+    b8, _, _ = plan(descs, n, s1, s2, PLAN_JACOBIAN)
     assert not any(x["stream"] for x in b8) and [x["code"] for x in b8 if x["kind"] == 1] == [TOO_LARGE]
     assert [x["pairs"] for x in b8 if x["kind"] == 1] == [2]
     # one row past the cap; a case-4 pair past the extension's 32 rows
-    b, _, _ = _plan(lib, descs, n, [k[512]], [k[513]], JS)
+    b, _, _ = plan(descs, n, [k[512]], [k[513]], JS)
     assert [(x["kind"], x["code"]) for x in b] == [(1, TOO_LARGE)]
-    b, _, _ = _plan(lib, descs, n, [k["gon"]], [k["cyl"]], JS | PLAN_CASE4)
+    b, _, _ = plan(descs, n, [k["gon"]], [k["cyl"]], JS | PLAN_CASE4)
     assert [(x["kind"], x["code"]) for x in b] == [(1, TOO_LARGE)]
-    b, _, _ = _plan(lib, descs, n, [k["gon"]], [k["cyl"]], JS)
+    b, _, _ = plan(descs, n, [k["gon"]], [k["cyl"]], JS)
     assert [(x["kind"], x["code"]) for x in b] == [(1, UNSUPPORTED)]
     # every other streamed (N, NSOC)
     for a, c, want in ((k["cap"], k[512], (5, 1)), (k[513], k["gon"], (6, 1)), (k["sph"], k[513], (4, 1))):
-        b, _, _ = _plan(lib, descs, n, [a], [c], JS)
+        b, _, _ = plan(descs, n, [a], [c], JS)
         assert [(x["stream"], x["N"], x["nsoc"]) for x in b] == [(1,) + want]
     # option 16 alone (the C-ABI's rule, restated by the x86 entry; the product library: the GPU file)
-    _plan(lib, descs, n, s1, s2, PLAN_JACOBIAN_STREAM, expect_rc=-1)
-    lib.dcol_emul_stream_jac_error.restype = ctypes.c_char_p
-    assert b"DCOL_PLAN_JACOBIAN" in lib.dcol_emul_stream_jac_error()
+    with pytest.raises(emul_lib.EmulError, match="DCOL_PLAN_JACOBIAN") as e:
+        plan(descs, n, s1, s2, PLAN_JACOBIAN_STREAM)
+    assert e.value.code == -1
     del keep
 
 
@@ -342,12 +212,12 @@ def test_header_constants_match_binding():
 
 # ---------------------------------------------------------------- 7. the sanitizer run
 def test_standalone_sanitizer_run():
-    """tests/emul_stream_jac/stream_jac_asan: the x86 Jacobian copies and a main of its own
+    """tests/emul/stream_jac_asan: the x86 Jacobian copies and a main of its own
     under the host address and undefined-behaviour sanitizers, on shapes it makes itself: 129,
     192, 193, 1,023 and 1,024 rows for (4, 0) and one pair of each other (N, NSOC), with and
     without a gradient; no Python in that process, nothing preloaded."""
-    subprocess.run(["make", "-C", DIR, "-s", "stream_jac_asan"], check=True)
-    r = subprocess.run([os.path.join(DIR, "stream_jac_asan")], capture_output=True, text=True)
+    emul_lib.load()   # (makes the program too)
+    r = subprocess.run([os.path.join(emul_lib.DIR, "stream_jac_asan")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
     got = re.findall(r"\(N, NSOC\) \((\d), (\d)\) rows\s+(\d+)", r.stdout)

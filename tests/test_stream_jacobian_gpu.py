@@ -9,11 +9,10 @@ import ctypes
 import numpy as np
 import pytest
 
+import jacobian_cases
 from conftest import alpha_close, grad_close
 from contact_jacobian_ref import contact_jacobian, tolerance
-from test_stream_jacobian import check_against_restatement, huge, ok_pairs
-from test_stream_rows import TOO_LARGE, UNSUPPORTED
-from test_stream_rows_gpu import bits, register, soa
+from stream_cases import TOO_LARGE, UNSUPPORTED, bits, check_against_restatement, huge, ok_pairs, register, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -76,9 +75,8 @@ def test_gpu_fixture_jacobian(full_run):
 # ---------------------------------------------------------------- 2. guarded window, 3. bitwise
 def _small_pairs(engine, n):
     """n pairs of at most 128 rows (synthetic_mixed) -> (s1, s2, pose1, pose2, [(name, index)])"""
-    from test_contact_jacobian import _golden, _pairs, _register
-    m, midx = _pairs("synthetic_mixed", n)
-    a, b = _register(engine, _golden("synthetic_mixed"))
+    m, midx = jacobian_cases.sample_pairs("synthetic_mixed", n)
+    a, b = jacobian_cases.registered(engine, m)
     return a[midx], b[midx], m["pose1"][midx], m["pose2"][midx], [("synthetic_mixed", int(i)) for i in midx]
 
 
@@ -117,9 +115,8 @@ def _run_plan(engine, plan, p1, p2, jacobian, guard=False):
 
 
 def _check_small(small, jac):
-    from test_contact_jacobian import _restated
     for j, (name, i) in enumerate(small):
-        J, cond, tol = _restated(name, i)
+        J, cond, tol = jacobian_cases.restated(name, i)
         err = np.abs(jac[j] - J).max()
         print(f"{name}[{i}]: err {err:.2e} tol {tol:.2e} cond(H) {cond:.1e}")
         assert err <= tol or cond > 1e10, (name, i, err, tol, cond)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG, REPO, alpha_close, golden_files, grad_close, load_golden
-from test_stream_rows import HUGE, TOO_LARGE, UNSUPPORTED, implicit_reference
+from stream_cases import FAKE, HUGE, TOO_LARGE, UNSUPPORTED, bits, implicit_reference, register, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -21,22 +21,6 @@ KEYS = ("status", "iters", "alpha", "contact", "grad")
 @pytest.fixture(scope="module")
 def huge():
     return load_golden(HUGE)
-
-
-def register(engine, d):
-    from dcol_amd import spec_from_arrays
-    ids = np.array([engine.register(spec_from_arrays(d, k)) for k in range(len(d["type"]))], dtype=np.int32)
-    return ids[d["s1"]], ids[d["s2"]]
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def soa(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x.T)).cuda()
 
 
 @pytest.fixture(scope="module")
@@ -177,7 +161,6 @@ def test_record_path_world2(huge, monkeypatch):
     import torch
     from dcol_amd import Engine, spec_from_arrays
     from dcol_amd.dist import REC, NativeComm, pack
-    from test_native_ranks import FAKE
     monkeypatch.setenv("DCOL_RCCL_LIB", FAKE)
     d = huge
     B, world = len(d["s1"]), 2
