@@ -148,6 +148,16 @@ __global__ void __launch_bounds__(256) reject_kernel(KArgs A, int32_t code) {
     }
 }
 
+// The first order of a hinted launch's table (plan_hints): a grid of nothing but filler waves
+// (hint_blocks 0, one window each) over zero hint bytes, i.e. the identity order with its
+// gathered ids and its "none" entries
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) hint_table_init(KArgs A) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    hint_fill<LPP>(A);
+#endif
+}
+
 }  // namespace dcol
 
 struct dcol_table {
@@ -212,18 +222,23 @@ struct dcol_plan {
     FusedSeg* d_segs = nullptr;  // lay.segs on the device
     void* d_susp = nullptr;      // DCOL_PLAN_SUSPEND scratch (one allocation for every such launch)
     bool jac = false;            // DCOL_PLAN_JACOBIAN: dense-row buckets (plan_layout_jac), no order hint
-    // Order-hint state (plan_hints; dcol_device.hpp hint_wave_slot): per stream the plan has
-    // run on, two zero-filled uint8[B] buffers (one allocation), indexed by global slot.  Run k
-    // on the stream reads buf[k % 2] and writes buf[(k + 1) % 2]: within one launch a window's
-    // early waves finish and write before its late waves read, so the two must differ; and
-    // per stream, because dcol_plan_run takes a const plan and runs concurrently on several
-    // streams -- the waves of a window must all see the same bytes.  Created lazily (never
-    // while the stream captures), freed at dcol_plan_destroy; streams past kHintStreams run
-    // without a hint.  mutable + mutex: dcol_plan_run's plan is const.
+    // Order-hint state (plan_hints; dcol_device.hpp hint_fill_window): per stream the plan has
+    // run on, two zero-filled uint8[B] buffers (one allocation), indexed by global slot, and
+    // two launch-order tables of one HintEntry per lane group of every hinted launch's padded
+    // grid (one allocation; 32 B per padded slot and stream in all), started at the identity
+    // order.  Run k on the stream solves in the order of tab[k % 2] and writes its counts to
+    // buf[k % 2]; its filler waves read buf[(k + 1) % 2] (run k - 1's counts) and write
+    // tab[(k + 1) % 2], which nothing of run k reads.  Per stream, because dcol_plan_run takes
+    // a const plan and runs concurrently on several streams.  Created lazily (never while the
+    // stream captures), freed at dcol_plan_destroy; streams past kHintStreams run without a
+    // hint.  mutable + mutex: dcol_plan_run's plan is const.
     static constexpr int kHintStreams = 8;
     struct HintState {
         hipStream_t stream = nullptr;
-        uint8_t* buf = nullptr;   // [2][B]
+        uint8_t* buf = nullptr;     // [2][B]
+        HintEntry* tab = nullptr;   // [2][entries]
+        int64_t entries = 0;
+        std::vector<int64_t> tab0;  // per launch: its base entry in a table, -1: not a hinted launch
         uint64_t runs = 0;
     };
     mutable std::mutex hint_mu;
@@ -588,8 +603,10 @@ int dcol_plan_destroy(dcol_plan* p) {
     }
     if (p->table && p->n_hints > 0) {
         DeviceGuard g(p->table->device);
-        for (int i = 0; i < p->n_hints; ++i)
+        for (int i = 0; i < p->n_hints; ++i) {
             if (p->hints[i].buf) (void)hipFree(p->hints[i].buf);
+            if (p->hints[i].tab) (void)hipFree(p->hints[i].tab);
+        }
     }
     delete p;
     return DCOL_SUCCESS;
@@ -661,20 +678,68 @@ int hint_waves() {
     return ww;
 }
 
-// The order-hint buffers of this run of p on st: *rd the previous run's iteration counts on
-// this stream (zeros before the first), *wr where this run leaves its own.  false: the run
-// goes without a hint (DCOL_NO_ORDER_HINT=1; a plan with no hinted launch; a first run on a
-// capturing stream; more than kHintStreams streams; no memory).  A run captured into a graph
-// keeps the pair it was captured with at every replay: it reads one buffer and writes the
-// other each time, a frozen, consistent order.
-bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t** wr) {
+// windows per filler wave (DCOL_HINT_FILL_WINDOWS, 1..8; A/B runs).  Swept 1 / 2 / 4 at 4
+// waves per window: DESIGN.md section 5
+int hint_fill_windows() {
+    static const int fw = [] {
+        const char* e = std::getenv("DCOL_HINT_FILL_WINDOWS");
+        return std::min(std::max(e ? std::atoi(e) : 1, 1), 8);
+    }();
+    return fw;
+}
+
+bool hinted_launch(const Launch& L) { return L.kind == 0 && !L.susp && !L.stream; }
+
+// the identity order of launch L (entries from tab0) into tab, on st; rd: zero hint bytes
+hipError_t hint_table_start(const dcol_plan* p, const Launch& L, const uint8_t* rd, HintEntry* tab, int64_t tab0,
+                            hipStream_t st) {
+    KArgs a{};
+    a.s1 = p->d_s1;
+    a.s2 = p->d_s2;
+    a.perm = p->d_perm;
+    a.B = p->B;
+    a.slot0 = L.slot0;
+    a.n = L.n;
+    a.hint_r = rd;
+    a.hint_ww = hint_waves();
+    a.hint_wins = hint_windows(L.n, L.lpp, a.hint_ww);
+    a.hint_tab_w = tab;
+    a.hint_tab0 = tab0;
+    a.hint_blocks = 0;
+    a.hint_fw = 1;
+    const dim3 grid((unsigned)hint_filler_blocks(a.hint_wins, 1)), block(kBlock);
+    switch (L.lpp) {
+        case 1: hipLaunchKernelGGL(hint_table_init<1>, grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL(hint_table_init<2>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(hint_table_init<4>, grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL(hint_table_init<8>, grid, block, 0, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// What a hinted run of p on st reads and writes (dcol_plan::HintState)
+struct HintRun {
+    const uint8_t* rd = nullptr;        // the previous run's iteration counts (zeros before it)
+    uint8_t* wr = nullptr;              // where this run leaves its own
+    const HintEntry* tab_r = nullptr;   // this run's order
+    HintEntry* tab_w = nullptr;         // where this run's filler waves leave the next run's
+    const int64_t* tab0 = nullptr;      // per launch of the plan: its base entry
+};
+
+// The order-hint state of this run of p on st.  false: the run goes without a hint
+// (DCOL_NO_ORDER_HINT=1; a plan with no hinted launch; a first run on a capturing stream; more
+// than kHintStreams streams; no memory).  A run captured into a graph keeps the buffers it was
+// captured with at every replay: the table it reads is never written by a replay, a frozen,
+// consistent order.
+bool plan_hints(const dcol_plan* p, hipStream_t st, HintRun* R) {
     static const bool off = [] {
         const char* e = std::getenv("DCOL_NO_ORDER_HINT");
         return e && *e && *e != '0';
     }();
     if (off || p->jac || p->lay.fused() || p->B >= (int64_t)1 << 31) return false;
     bool any = false;
-    for (const Launch& L : p->launches) any = any || (L.kind == 0 && !L.susp);
+    for (const Launch& L : p->launches) any = any || hinted_launch(L);
     if (!any) return false;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
@@ -685,20 +750,47 @@ bool plan_hints(const dcol_plan* p, hipStream_t st, const uint8_t** rd, uint8_t*
         if (p->hints[i].stream == st) S = &p->hints[i];
     if (!S) {
         if (capturing || p->n_hints >= dcol_plan::kHintStreams) return false;
+        // every hinted launch's share of a table, in launch order
+        const int ww = hint_waves();
+        std::vector<int64_t> tab0(p->launches.size(), -1);
+        int64_t entries = 0;
+        for (size_t i = 0; i < p->launches.size(); ++i) {
+            const Launch& L = p->launches[i];
+            if (!hinted_launch(L)) continue;
+            tab0[i] = entries;
+            entries += (int64_t)hint_windows(L.n, L.lpp, ww) * ww * (64 / L.lpp);
+        }
         uint8_t* b = nullptr;
-        if (hipMalloc(&b, 2 * (size_t)p->B) != hipSuccess || hipMemsetAsync(b, 0, 2 * (size_t)p->B, st) != hipSuccess) {
+        HintEntry* tab = nullptr;
+        bool ok = hipMalloc(&b, 2 * (size_t)p->B) == hipSuccess &&
+                  hipMalloc(&tab, 2 * (size_t)entries * sizeof(HintEntry)) == hipSuccess &&
+                  hipMemsetAsync(b, 0, 2 * (size_t)p->B, st) == hipSuccess;
+        for (size_t i = 0; ok && i < p->launches.size(); ++i)
+            for (int k = 0; ok && k < 2 && tab0[i] >= 0; ++k)
+                ok = hint_table_start(p, p->launches[i], b, tab + k * entries, tab0[i], st) == hipSuccess;
+        if (!ok) {
+            // (a start kernel already queued may still run: let it before its memory goes)
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(st);
             (void)hipGetLastError();
             if (b) (void)hipFree(b);
+            if (tab) (void)hipFree(tab);
             return false;
         }
         S = &p->hints[p->n_hints++];
         S->stream = st;
         S->buf = b;
+        S->tab = tab;
+        S->entries = entries;
+        S->tab0 = std::move(tab0);
         S->runs = 0;
     }
     const uint64_t k = S->runs & 1;
-    *rd = S->buf + k * (size_t)p->B;
-    *wr = S->buf + (k ^ 1) * (size_t)p->B;
+    R->wr = S->buf + k * (size_t)p->B;
+    R->rd = S->buf + (k ^ 1) * (size_t)p->B;
+    R->tab_r = S->tab + k * S->entries;
+    R->tab_w = S->tab + (k ^ 1) * S->entries;
+    R->tab0 = S->tab0.data();
     if (!capturing) ++S->runs;
     return true;
 }
@@ -764,10 +856,10 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     const int fdonly = (flags & (DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)) ? 0 : LF_FDONLY;
     const bool fan = p->lay.lanes > 1 && p->fork;
     hipError_t e = hipSuccess;
-    // (before the fork: the side streams' launches then follow a new state's zero fill)
-    const uint8_t* hint_r = nullptr;
-    uint8_t* hint_w = nullptr;
-    const bool hinted = hint && plan_hints(p, st, &hint_r, &hint_w);
+    // (before the fork: the side streams' launches then follow a new state's zero fill and
+    // first tables)
+    HintRun hr;
+    const bool hinted = hint && plan_hints(p, st, &hr);
     if (fan) {
         e = hipEventRecord(p->fork, st);
         for (int l = 1; e == hipSuccess && l < p->lay.lanes; ++l) e = hipStreamWaitEvent(t->side[l - 1], p->fork, 0);
@@ -775,7 +867,8 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
     }
     const size_t nl = p->launches.size();
     for (size_t li = 0; li < nl; ++li) {
-        const Launch& L = p->launches[p->lay.issue.size() == nl ? (size_t)p->lay.issue[li] : li];
+        const size_t lx = p->lay.issue.size() == nl ? (size_t)p->lay.issue[li] : li;
+        const Launch& L = p->launches[lx];
         if (L.kind == 0 && p->lay.fused()) continue;   // covered by the fused launch below
         a.slot0 = L.slot0;
         a.n = L.n;
@@ -803,10 +896,15 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
                                   ? LF_SPLIT : 0;
             KArgs b = a;
             if (hinted) {   // every solve bucket of the "one bucket" and "buckets" forms
-                b.hint_r = hint_r;
-                b.hint_w = hint_w;
+                b.hint_r = hr.rd;
+                b.hint_w = hr.wr;
                 b.hint_ww = hint_waves();
                 b.hint_wins = hint_windows(L.n, L.lpp, b.hint_ww);
+                b.hint_tab_r = hr.tab_r;
+                b.hint_tab_w = hr.tab_w;
+                b.hint_tab0 = hr.tab0[lx];
+                b.hint_blocks = hint_solve_blocks(b.hint_wins, b.hint_ww);
+                b.hint_fw = hint_fill_windows();
             }
             e = launch_variant(L.N, L.nsoc, L.omax, L.lpp, L.flags() | fdonly | split, b, ls, L.oe);
         }

@@ -147,6 +147,15 @@ DCOL_HD double rec_ints(int32_t status, int32_t iters) {
 #endif
 }
 
+// One entry of a hinted launch's launch-order table (hint_fill_window below): what the lane
+// group at that place of the grid solves.  pi: the pair (after perm), -1: nothing (a phantom
+// window or wave of the padded grid, the ragged end); k1 / k2: its shape ids; hs: its launch
+// slot, where the epilogue leaves this run's iteration count.
+struct alignas(16) HintEntry {
+    int32_t pi, k1, k2, hs;
+};
+static_assert(sizeof(HintEntry) == 16, "HintEntry layout");
+
 struct KArgs {
     const DevShape* __restrict__ shapes;
     const DevRow* __restrict__ rows;
@@ -182,16 +191,25 @@ struct KArgs {
     int32_t* susp_pi;                   // [susp_cap] pair index (slot index into perm space)
     double* susp_state;                 // [fields][susp_cap]: it, x[N], then (s, z, r) per lane row
     int64_t susp_cap;
-    // Window-local order hint (hint_wave_slot below; dcol_capi.cpp HintState): the iteration
-    // counts of the (plan, stream)'s previous run, one byte per launch slot, indexed by the
-    // global slot slot0 + slot.  hint_r is read by the prologue, hint_w written by the
-    // epilogue (the other buffer of the pair); both nullptr and hint_wins 0: no hint, the
-    // launch maps thread -> slot linearly.  hint_wins: windows of the launch padded to a
-    // multiple of 8 (the grid is hint_wins * hint_ww waves); hint_ww: waves per window.
+    // Window-local order hint (hint_fill_window below; dcol_capi.cpp HintState).  hint_r /
+    // hint_w: iteration counts of the (plan, stream)'s runs, one byte per launch slot, indexed
+    // by the global slot slot0 + slot: hint_w is written by this run's epilogues, hint_r (the
+    // other buffer of the pair, complete: the previous run wrote it) is read by this run's
+    // filler waves.  Both nullptr and hint_wins 0: no hint, the launch maps thread -> slot
+    // linearly.  hint_wins: windows of the launch padded to a multiple of 8; hint_ww: waves per
+    // window.  The grid is hint_blocks workgroups of solve waves (hint_wins * hint_ww waves),
+    // then the filler waves, hint_fw windows each.  A solve wave reads its lane groups' entries
+    // from hint_tab_r + hint_tab0 (the order an earlier run's filler waves left); the filler
+    // waves leave the next run's order in hint_tab_w + hint_tab0 (the other table of the pair).
     const uint8_t* __restrict__ hint_r = nullptr;
     uint8_t* __restrict__ hint_w = nullptr;
     int32_t hint_wins = 0;
     int32_t hint_ww = 0;
+    const HintEntry* __restrict__ hint_tab_r = nullptr;
+    HintEntry* __restrict__ hint_tab_w = nullptr;
+    int64_t hint_tab0 = 0;
+    int32_t hint_blocks = 0;
+    int32_t hint_fw = 1;
     // [4][12][B] contact-point Jacobian d[x0, x1, x2, alpha] / d[r1, p1, r2, p2], component
     // (k, j) at (12 k + j) B + pi; written by the JAC copies (solve_one JAC) of a run with
     // F_JAC, nullptr: none
@@ -2846,15 +2864,26 @@ constexpr bool kGlds = true;
 // their hint bytes (the pair's iteration count of the previous run, clamped to 0..63), and
 // the window's wave of rank r takes positions [r * 64 / LPP, (r + 1) * 64 / LPP) of that
 // order: pairs of similar cost share a wave, the slowest wave has rank 0.  Equal hints (the
-// zero-filled first run) give the identity, i.e. contiguous slots per wave.  Any bytes give
-// a permutation of the window's slots, so every slot is solved exactly once as long as the
-// window's waves read the same bytes (dcol_capi.cpp: one buffer pair per plan and stream).
+// zero-filled first runs) give the identity, i.e. contiguous slots per wave.  Any bytes give
+// a permutation of the window's slots, so every slot is solved exactly once.
+//
+// No solve wave sorts.  A window's order is computed once, by a filler wave appended to the
+// grid of an earlier run (blocks past hint_blocks: they start when wave slots free up, in
+// the launch's drain), which leaves it as a table in launch order: one HintEntry per lane
+// group of the padded grid.  Wave w of the launch is rank w / hint_wins of window
+// w % hint_wins -- every window's slowest wave is dispatched first, and with hint_wins a
+// multiple of 8 a window's waves share blockIdx % 8 -- and its lane group g reads entry
+// w * 64 / LPP + g: the head of a solve wave is one coalesced load at an address that depends
+// on blockIdx / threadIdx only.  Run k of a (plan, stream) reads table k % 2 and writes its
+// counts into byte buffer k % 2; its filler waves read byte buffer (k - 1) % 2 -- complete,
+// the launches are stream-ordered -- and write table (k + 1) % 2, which no wave of run k
+// reads: no flag, fence or atomic.  The order of run k so comes from the counts of run k - 2.
 // ------------------------------------------------------------------------------------
 constexpr int kHintWavesMax = 8;   // waves per window, at most (the keys of a window sit in registers)
 constexpr int kHintWavesDefault = 4;   // measured 4 / 8 / 16 on configs[3]: DESIGN.md section 5
 DCOL_HD int hint_key(uint8_t h) { return h > 63 ? 63 : (int)h; }
 // The rule in scalar form: the position of slot i of a window of len slots with hint bytes
-// h[0 .. len) in the window's order (tests/emul_hint checks it; hint_wave_slot is its wave form).
+// h[0 .. len) in the window's order (tests/emul_hint checks it; hint_fill_window is its wave form).
 DCOL_HD int hint_position(const uint8_t* h, int len, int i) {
     const int k = hint_key(h[i]);
     int p = 0;
@@ -2864,29 +2893,59 @@ DCOL_HD int hint_position(const uint8_t* h, int len, int i) {
     }
     return p;
 }
+// The table's position arithmetic (tests/hint_table checks it on x86).  ppw: slots per wave
+// (64 / LPP); ws: slots per window (ww * ppw).
+// Slots of window win of a launch of n slots: ws, fewer in the ragged last one, 0 in a phantom
+DCOL_HD int hint_window_len(int64_t n, int64_t win, int ws) {
+    const int64_t left = n - win * ws;
+    return left <= 0 ? 0 : (int)(left < ws ? left : ws);
+}
+// The entry (relative to the launch's base) of position pos of window win: the wave of rank
+// pos / ppw of the window is wave rank * wins + win of the launch
+DCOL_HD int64_t hint_entry_index(int64_t win, int pos, int ppw, int32_t wins) {
+    return ((int64_t)(pos / ppw) * wins + win) * ppw + pos % ppw;
+}
+// The entry of launch slot `slot`; the entry of a position past the window's length
+DCOL_HD HintEntry hint_entry(const KArgs& A, int64_t slot) {
+    const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
+    return HintEntry{(int32_t)pi, A.s1[pi], A.s2[pi], (int32_t)slot};
+}
+DCOL_HD HintEntry hint_entry_none() { return HintEntry{-1, -1, -1, -1}; }
+// What a filler wave does for window win, in scalar form: every slot's entry at the place of
+// its position, "none" at the positions past the window's length
+DCOL_HD void hint_fill_window_scalar(const KArgs& A, int64_t win, int ppw) {
+    const int ws = A.hint_ww * ppw;
+    const int len = hint_window_len(A.n, win, ws);
+    HintEntry* tab = A.hint_tab_w + A.hint_tab0;
+    const uint8_t* h = A.hint_r + A.slot0 + win * ws;
+    for (int i = 0; i < len; ++i)
+        tab[hint_entry_index(win, hint_position(h, len, i), ppw, A.hint_wins)] = hint_entry(A, win * ws + i);
+    for (int p = len; p < ws; ++p) tab[hint_entry_index(win, p, ppw, A.hint_wins)] = hint_entry_none();
+}
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// The launch slot of this lane's group under the hint, or -1 if the group has none (a
-// phantom window or wave of the padded grid, the ragged end).  Called by every lane of the
-// wave (ballots); the lanes of a group get the same answer.  Wave w of the launch is rank
-// w / hint_wins of window w % hint_wins: every window's slowest wave is dispatched first,
-// and with hint_wins a multiple of 8 a window's waves share blockIdx % 8.
+// A filler wave's work for window win (wave-uniform) of the launch: the table entries of the
+// window's hint_ww * 64 / LPP positions into hint_tab_w, from the hint bytes in hint_r.
+// Called by every lane of the wave (ballots).
 // Lane K of the wave doubles as the counter of key K (64 lanes, 64 keys): per chunk of 64
 // slots six ballots of the key bits give each lane both the lanes holding its own key and
 // the lanes holding key K.
 template <int LPP>
-__device__ __forceinline__ int32_t hint_wave_slot(const KArgs& A) {
+__device__ __forceinline__ void hint_fill_window(const KArgs& A, int64_t win) {
     constexpr int PPW = 64 / LPP;   // slots per wave
     constexpr int JMAX = (kHintWavesMax * PPW + 63) / 64;   // chunks of 64 slots per window, at most
-    __shared__ uint16_t order[kSolveBlock / 64][PPW];   // this wave's share of the window's order
-    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
-    const uint32_t w = blockIdx.x * (uint32_t)(kSolveBlock / 64) + (uint32_t)wv;
-    const int rank = (int)(w / (uint32_t)A.hint_wins);
-    const int64_t win = w % (uint32_t)A.hint_wins;
+    const int lane = (int)(threadIdx.x & 63);
     const int ws = A.hint_ww * PPW;   // slots per window
     const int64_t base = win * ws;
-    if (rank >= A.hint_ww || base >= A.n) return -1;   // (wave-uniform)
-    const int len = (int)(A.n - base < ws ? A.n - base : ws);
+    const int len = hint_window_len(A.n, win, ws);   // (wave-uniform)
+    HintEntry* __restrict__ tab = A.hint_tab_w + A.hint_tab0;
+    // positions past the window's length (the ragged end, a phantom window): nothing to solve
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) {
+        const int p = len + j * 64 + lane;
+        if (p < ws) tab[hint_entry_index(win, p, PPW, A.hint_wins)] = hint_entry_none();
+    }
+    if (len == 0) return;
     const uint8_t* __restrict__ h = A.hint_r + A.slot0 + base;
     // the window's keys, one load per chunk, all in flight together; -1: past the window's end
     int key[JMAX];
@@ -2922,7 +2981,6 @@ __device__ __forceinline__ int32_t hint_wave_slot(const KArgs& A) {
     start -= cnt;
     // pass 2: each slot's position = its key's run start + the equal keys before it
     const unsigned long long below = (1ull << lane) - 1ull;
-    const int lo = rank * PPW;
 #pragma unroll
     for (int j = 0; j < JMAX; ++j) {
         if (j * 64 < len) {
@@ -2933,19 +2991,25 @@ __device__ __forceinline__ int32_t hint_wave_slot(const KArgs& A) {
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(((key[j] >> b) & 1) != 0);
                 mine &= ((key[j] >> b) & 1) ? m : ~m;
             }
-            const int p = __shfl(start, key[j] & 63, 64) + __popcll(mine & below) - lo;
-            if (v && p >= 0 && p < PPW) order[wv][p] = (uint16_t)(j * 64 + lane);
+            const int p = __shfl(start, key[j] & 63, 64) + __popcll(mine & below);
+            if (v) tab[hint_entry_index(win, p, PPW, A.hint_wins)] = hint_entry(A, base + j * 64 + lane);
             start += cntc[j];   // key K's slots of this chunk are placed
         }
     }
-    // the wave's own writes, read back by its other lanes: LDS operations of one wave
-    // execute in order, so only the compiler has to keep them so (no workgroup barrier)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const int g = lane / LPP;
-    if (lo + g >= len) return -1;
-    return (int32_t)(base + order[wv][g]);
+}
+
+// The filler waves of a hinted launch (the blocks past hint_blocks): wave f takes windows
+// [f * hint_fw, (f + 1) * hint_fw) of the launch's hint_wins
+template <int LPP>
+__device__ __forceinline__ void hint_fill(const KArgs& A) {
+    const int64_t f = ((int64_t)blockIdx.x - A.hint_blocks) * (kSolveBlock / 64) +
+                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#pragma unroll 1
+    for (int c = 0; c < A.hint_fw; ++c) {
+        const int64_t win = f * A.hint_fw + c;
+        if (win >= A.hint_wins) return;   // (wave-uniform)
+        hint_fill_window<LPP>(A, win);
+    }
 }
 #endif
 
@@ -2955,20 +3019,38 @@ __global__ void __launch_bounds__(kSolveBlock, WPS % 10) prox_kernel(KArgs A) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t slot = t / LPP;
     const int q = (int)(t % LPP);
-    int32_t hs = -1;
+    int64_t pi = 0;
+    int32_t k1 = -1, k2 = -1, hs = -1;
+    bool listed = false;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr ((FL & 16) == 0) {   // (a suspend / resume main launch carries no hint)
+    if constexpr ((FL & 16) == 0 && !JAC) {   // (suspend / resume main launches and Jacobian runs carry no hint)
         if (A.hint_wins > 0) {
-            hs = hint_wave_slot<LPP>(A);
-            if (hs < 0) return;
-            slot = hs;
+            if ((int32_t)blockIdx.x >= A.hint_blocks) {   // (wave-uniform) a filler wave: the next run's order
+                hint_fill<LPP>(A);
+                return;
+            }
+            // entry w * 64 / LPP + g = t / LPP, as one 16-byte load (a struct load is split at
+            // the test of pi: two dependent rounds)
+            typedef int32_t v4i __attribute__((ext_vector_type(4)));
+            const v4i e = *reinterpret_cast<const v4i*>(A.hint_tab_r + A.hint_tab0 + slot);
+            if (e.x < 0) return;
+            pi = e.x;
+            k1 = e.y;
+            k2 = e.z;
+            hs = e.w;
+            listed = true;
         }
     }
 #endif
-    if (slot >= A.n) return;
-    const int64_t pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
+    if (!listed) {
+        if (slot >= A.n) return;
+        pi = A.perm ? (int64_t)A.perm[A.slot0 + slot] : (A.slot0 + slot);
+        k1 = A.s1[pi];
+        k2 = A.s2[pi];
+    }
+    __builtin_assume(k1 >= 0 && k2 >= 0);   // shape ids: solve_one takes them as given
     solve_one<N, NSOC, OMAX, LPP, (FL & 1) != 0, (FL & 2) != 0, (FL & 4) != 0, OE, (FL & 16) ? 1 : 0,
-              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0, JAC>(A, pi, q, -1, -1, -1, hs);
+              kGlds && WPS >= 10, (FL & 8) != 0, (FL & 64) != 0, (FL & 32) != 0, JAC>(A, pi, q, -1, k1, k2, hs);
 }
 
 // The resume launch of a suspend / resume pair: one lane group per continuation entry;

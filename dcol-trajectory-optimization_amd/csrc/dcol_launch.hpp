@@ -11,11 +11,17 @@ constexpr int kBlock = kSolveBlock;   // threads per workgroup of the solve kern
 constexpr int kSideStreams = 7;   // capacity of the extra streams for concurrent variant launches
                                   // (dcol_plan.hpp PlanPolicy::side_streams: 3 by default, DCOL_SIDE_STREAMS)
 // Grid of a prox_kernel launch: n * lpp threads mapped linearly, or -- with an order hint
-// (KArgs hint_wins > 0, dcol_device.hpp hint_wave_slot) -- hint_ww waves for each of the
-// hint_wins windows, phantom ones included (they exit at once)
+// (KArgs hint_wins > 0, dcol_device.hpp hint_fill_window) -- hint_ww solve waves for each of
+// the hint_wins windows, phantom ones included (they exit at once), in hint_blocks
+// workgroups, then the filler waves that leave the next run's order, hint_fw windows each
+constexpr int kHintWpb = kBlock / 64;   // waves per workgroup
+static_assert(8 % kHintWpb == 0, "hint_wins is a multiple of 8: whole workgroups of solve waves");
+inline int32_t hint_solve_blocks(int32_t wins, int ww) { return (int32_t)((int64_t)wins * ww / kHintWpb); }
+inline int64_t hint_filler_blocks(int32_t wins, int fw) {
+    return (((int64_t)wins + fw - 1) / fw + kHintWpb - 1) / kHintWpb;
+}
 inline int64_t solve_grid(const KArgs& a, int lpp) {
-    constexpr int wpb = kBlock / 64;   // waves per workgroup
-    if (a.hint_wins > 0) return ((int64_t)a.hint_wins * a.hint_ww + wpb - 1) / wpb;
+    if (a.hint_wins > 0) return (int64_t)a.hint_blocks + hint_filler_blocks(a.hint_wins, a.hint_fw);
     return (a.n * lpp + kBlock - 1) / kBlock;
 }
 // windows of a launch of n slots at ww waves per window, padded to a multiple of 8: a window's

@@ -235,13 +235,15 @@ int dcol_plan_suspended(const dcol_plan* plan, int64_t* n);
  * no allocation while the stream is capturing, so the call can be captured into a hipGraph.
  *
  * Order hint.  A plan of the DCOL_FORM_BUCKETS form keeps, per stream it has been run on
- * (up to 8; further streams run without), two bytes per pair of device memory: each run
- * leaves every pair's iteration count there, and the stream's next run uses it to put
- * pairs of similar cost -- inside windows of a few hundred consecutive pairs -- into the
- * same wave, the slowest wave first.  Only which lane group solves which pair changes; the
+ * (up to 8; further streams run without), two bytes and two 16-byte launch-order entries
+ * per pair of device memory (34 B per pair, padded to whole windows): each run leaves every
+ * pair's iteration count there and, from the counts of the run before it, the order of the
+ * stream's next run, which puts pairs of similar cost -- inside windows of a few hundred
+ * consecutive pairs -- into the same wave, the slowest wave first: a run's order comes from
+ * the counts of the run two before it.  Only which lane group solves which pair changes; the
  * outputs are bitwise those of a run without the hint (DCOL_NO_ORDER_HINT=1; the window is
  * DCOL_HINT_WAVES waves, 1..8, default 4).  The state is allocated by the first run on a stream
- * that is not capturing (one hipMalloc, zero-filled on that stream) and freed by
+ * that is not capturing (two hipMallocs, filled on that stream) and freed by
  * dcol_plan_destroy, so destroy the plan after its runs have completed, as before.  The
  * runs of one plan on one stream must be issued by one thread at a time; different
  * streams are independent.
