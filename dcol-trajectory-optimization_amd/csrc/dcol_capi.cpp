@@ -345,8 +345,8 @@ const char* dcol_status_string(int32_t s) {
         case DCOL_NOT_PD: return "Matrix is not positive definite";
         case DCOL_NONFINITE: return "array must not contain infs or NaNs";
         case DCOL_TOO_LARGE:
-            return "pair exceeds the engine's orthant-row capacity (1024 rows; 32 for a case-4 pair, 128 with the "
-                   "contact-point Jacobian)";
+            return "pair exceeds the engine's orthant-row capacity (1024 rows; 32 for a case-4 pair without "
+                   "DCOL_PLAN_CASE4_STREAM, 128 with the contact-point Jacobian)";
         default: return "unknown status";
     }
 }
@@ -519,9 +519,9 @@ int ensure_fanout(const dcol_table* tc, dcol_plan* p) {
 
 // The plan's layout under the process's policy, and its launches
 int plan_build(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, bool case4, bool allow_fuse,
-               dcol_plan* p, bool jac = false, bool jac_stream = false) {
-    const int rc = jac ? plan_layout_jac(t->shapes, t->simds, B, s1, s2, case4, plan_policy(), p->lay, jac_stream)
-                       : plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay);
+               dcol_plan* p, bool jac = false, bool jac_stream = false, bool case4_stream = false) {
+    const int rc = jac ? plan_layout_jac(t->shapes, t->simds, B, s1, s2, case4, plan_policy(), p->lay, jac_stream, case4_stream)
+                       : plan_layout(t->shapes, t->simds, B, s1, s2, case4, allow_fuse, plan_policy(), p->lay, case4_stream);
     if (rc != DCOL_SUCCESS) return rc;
     p->jac = jac;
     p->table = t;
@@ -540,8 +540,11 @@ int dcol_plan_create(const dcol_table* t, int64_t B, const int32_t* s1, const in
 int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const int32_t* s2, int32_t options,
                         dcol_plan** out) {
     if (!t || !out || B < 0 || (B > 0 && (!s1 || !s2))) return fail(DCOL_ERR_ARG, "dcol_plan_create: bad arguments");
-    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND | DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM))
+    if (options & ~(DCOL_PLAN_CASE4 | DCOL_PLAN_NO_FUSE | DCOL_PLAN_SUSPEND | DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM |
+                    DCOL_PLAN_CASE4_STREAM))
         return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: unknown option bits");
+    if ((options & DCOL_PLAN_CASE4_STREAM) && !(options & DCOL_PLAN_CASE4))
+        return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: DCOL_PLAN_CASE4_STREAM needs DCOL_PLAN_CASE4");
     if ((options & DCOL_PLAN_JACOBIAN_STREAM) && !(options & DCOL_PLAN_JACOBIAN))
         return fail(DCOL_ERR_ARG, "dcol_plan_create_ex: DCOL_PLAN_JACOBIAN_STREAM needs DCOL_PLAN_JACOBIAN");
     if ((options & DCOL_PLAN_JACOBIAN) && (options & DCOL_PLAN_SUSPEND))
@@ -551,7 +554,8 @@ int dcol_plan_create_ex(const dcol_table* t, int64_t B, const int32_t* s1, const
     auto* p = new (std::nothrow) dcol_plan();
     if (!p) return fail(DCOL_ERR_NOMEM, "host allocation failed");
     int rc = plan_build(t, B, s1, s2, (options & DCOL_PLAN_CASE4) != 0, (options & DCOL_PLAN_NO_FUSE) == 0, p,
-                        (options & DCOL_PLAN_JACOBIAN) != 0, (options & DCOL_PLAN_JACOBIAN_STREAM) != 0);
+                        (options & DCOL_PLAN_JACOBIAN) != 0, (options & DCOL_PLAN_JACOBIAN_STREAM) != 0,
+                        (options & DCOL_PLAN_CASE4_STREAM) != 0);
     if (rc != DCOL_SUCCESS) {
         delete p;
         return rc;
@@ -888,9 +892,11 @@ int plan_run_rec(const dcol_plan* p, const double* pose1, const double* pose2, d
             e = hipMemsetAsync(L.d_susp_count, 0, sizeof(int32_t), ls);
             if (e == hipSuccess) e = launch_susp(L.N, L.nsoc, L.omax, L.lpp, L.flags(), L.oe, b, ls);
         } else if (want_jac) {   // (a Jacobian plan: dense rows or a streamed bucket's JAC copy, no hint)
-            e = L.stream ? launch_stream_jac(L.N, L.nsoc, a, ls) : launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls);
+            // (N >= 7: the case-4 streamed instances, units of their own)
+            e = !L.stream ? launch_jac(L.N, L.nsoc, L.omax, L.lpp, a, ls)
+                          : (L.N >= 7 ? launch_stream_c4_jac(L.N, L.nsoc, a, ls) : launch_stream_jac(L.N, L.nsoc, a, ls));
         } else if (L.stream) {   // a wave per pair: nothing to regroup, so no hint
-            e = launch_stream(L.N, L.nsoc, a, ls);
+            e = L.N >= 7 ? launch_stream_c4(L.N, L.nsoc, a, ls) : launch_stream(L.N, L.nsoc, a, ls);
         } else {
             const int split = (L.oe > 0 && L.lpp == 2 && split_enabled() && split_built(L.N, L.nsoc, L.omax, L.oe))
                                   ? LF_SPLIT : 0;
@@ -1017,15 +1023,20 @@ int dcol_prox_pair(const dcol_table* tc, int32_t s1, int32_t s2, const double* p
         __atomic_store_n(&t->pair_host, hb, __ATOMIC_RELEASE);
     }
     const int64_t key = (int64_t)s1 * ns + s2;
-    const bool c4 = (flags & DCOL_CASE4) != 0;
-    const int64_t ck = c4 ? -1 - key : key;   // case-4 plans apart
+    // (DCOL_CASE4_STREAM implies DCOL_CASE4; both are host-call flags, stripped below)
+    const bool c4s = (flags & DCOL_CASE4_STREAM) != 0;
+    const bool c4 = c4s || (flags & DCOL_CASE4) != 0;
+    flags &= ~(DCOL_CASE4 | DCOL_CASE4_STREAM);
+    const int64_t nkeys = (int64_t)ns * ns;
+    const int64_t ck = c4s ? -1 - nkeys - key : (c4 ? -1 - key : key);   // case-4 plans apart, streamed ones too
     dcol_plan* plan = nullptr;
     auto it = t->pair_plans.find(ck);
     if (it != t->pair_plans.end()) {
         t->pair_lru.splice(t->pair_lru.begin(), t->pair_lru, it->second);   // now the most recent
         plan = it->second->second;
     } else {
-        const int rc = dcol_plan_create_ex(t, 1, &s1, &s2, c4 ? DCOL_PLAN_CASE4 : 0, &plan);
+        const int rc = dcol_plan_create_ex(t, 1, &s1, &s2,
+                                           c4s ? (DCOL_PLAN_CASE4 | DCOL_PLAN_CASE4_STREAM) : (c4 ? DCOL_PLAN_CASE4 : 0), &plan);
         if (rc != DCOL_SUCCESS) return rc;
         // the least recently used plan makes room (no launch of it is in flight: every call
         // synchronises its stream before returning)
@@ -1320,7 +1331,11 @@ static int prox_batch_host(const dcol_table* tc, int64_t B, const int32_t* s1, c
     // (DCOL_JACOBIAN_STREAM: a host-call flag like DCOL_CASE4, not a kernel flag)
     const bool jac_stream = jac != nullptr && (flags & DCOL_JACOBIAN_STREAM) != 0;
     flags &= ~DCOL_JACOBIAN_STREAM;
-    int rc = plan_build(t, B, s1, s2, (flags & DCOL_CASE4) != 0, true, &p, jac != nullptr, jac_stream);
+    // (DCOL_CASE4_STREAM: likewise; it implies DCOL_CASE4)
+    const bool case4_stream = (flags & DCOL_CASE4_STREAM) != 0;
+    const bool case4 = case4_stream || (flags & DCOL_CASE4) != 0;
+    flags &= ~DCOL_CASE4_STREAM;
+    int rc = plan_build(t, B, s1, s2, case4, true, &p, jac != nullptr, jac_stream, case4_stream);
     if (rc != DCOL_SUCCESS) return rc;
     rc = ensure_fanout(t, &p);
     if (rc != DCOL_SUCCESS) return rc;

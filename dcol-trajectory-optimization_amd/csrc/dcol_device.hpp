@@ -3097,6 +3097,12 @@ constexpr int kStreamLdsDoubles = kStreamFields * kStreamMaxRows;   // 40 KiB pe
 // the built instances (N, NSOC): the combine cases 1-3 in which a polytope or a polygon can
 // bring many rows (dcol_kernels_stream.hip; dcol_host.hpp classify routes only these)
 #define DCOL_STREAM_SHAPES(X) X(4, 0) X(4, 1) X(5, 1) X(6, 1) X(6, 2)
+// the case-4 instances (both primitives with extra columns; DCOL_PLAN_CASE4_STREAM): polygon x
+// capsule / cylinder (7, 2) and polygon x polygon (8, 2), a list of its own -- the instances
+// above are built, routed and tested as before (dcol_kernels_stream_c4.hip; dcol_host.hpp
+// classify routes these only when asked).  An N >= 7 pair is always case 4; the case-4 (6, 2)
+// pairs are capsule / cylinder pairs of at most 8 rows and never stream.
+#define DCOL_STREAM_CASE4_SHAPES(X) X(7, 2) X(8, 2)
 
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ double readlane_d(double v, int l) {
@@ -3148,6 +3154,8 @@ struct StreamSolver {
     lds_d* ws;                 // this lane's first element of the row state
     const double* __restrict__ rows;
     int lane, o1, o, nslot, ro1, ro2;
+    int xo2;                   // N >= 7 (case 4): first extra column of primitive 2 minus 4, S1.n_extra
+                               // (Solver::xo2); not used below N = 7
     double Qe1[9], re1[3], Qe2[9], re2[3];
     // SOC blocks (dense rows, every lane the same values); rs holds h until initialize()
     double Gs[SSA][4][N], ss[SSA][4], zs[SSA][4], rs[SSA][4];
@@ -3173,10 +3181,17 @@ struct StreamSolver {
         g[1] = Q[3] * a0 + Q[4] * a1 + Q[5] * a2;
         g[2] = Q[6] * a0 + Q[7] * a1 + Q[8] * a2;
         g[3] = q1.y;
-        // cases 1-3: the one primitive with extra columns puts them at columns 4, 5; the
-        // other's descriptors carry zeros there
-        if constexpr (N > 4) g[4] = q2.x;
-        if constexpr (N > 5) g[5] = q2.y;
+        if constexpr (N >= 7) {
+            // case 4: primitive 2's extra columns follow primitive 1's (Solver::orth_row)
+            const int off = p2 ? xo2 : 0;
+#pragma unroll
+            for (int j = 4; j < N; ++j) g[j] = FS::excol(j, off, q2.x, q2.y);
+        } else {
+            // cases 1-3: the one primitive with extra columns puts them at columns 4, 5; the
+            // other's descriptors carry zeros there
+            if constexpr (N > 4) g[4] = q2.x;
+            if constexpr (N > 5) g[5] = q2.y;
+        }
         h = g[0] * re[0] + g[1] * re[1] + g[2] * re[2];
     }
     DCOL_HD static double dotn(const double* g, const double* v) {
@@ -3203,6 +3218,7 @@ struct StreamSolver {
         nslot = (o + LANES - 1) / LANES;
         ro1 = S1.row_off;
         ro2 = S2.row_off;
+        if constexpr (N >= 7) xo2 = S1.n_extra;
 #pragma unroll
         for (int c = 0; c < 9; ++c) {
             Qe1[c] = F1.Qe[c];
@@ -3225,8 +3241,10 @@ struct StreamSolver {
             for (int c = 0; c < 9; ++c) Q[c] = p2 ? Qe2[c] : Qe1[c];
 #pragma unroll
             for (int c = 0; c < 3; ++c) re[c] = p2 ? re2[c] : re1[c];
+            int off = 0;   // the block's extra columns: after primitive 1's for primitive 2 of a case-4 pair
+            if constexpr (N >= 7) off = p2 ? xo2 : 0;
             FS::soc_rows(soc_kind[b], p2 ? S2.R : S1.R, p2 ? S2.cone_c : S1.cone_c, p2 ? S2.tanb : S1.tanb,
-                         p2 ? S2.n_extra : S1.n_extra, 0, Q, re, Gs[b], rs[b]);
+                         p2 ? S2.n_extra : S1.n_extra, off, Q, re, Gs[b], rs[b]);
         }
     }
 
@@ -3841,9 +3859,10 @@ DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamS
             const bool imp_ok = imp && P.implicit_v(W);
             Agg agA[2];
             P.aggregates(S1, S2, imp, W, agZ, agA);
-            typename Slv::FS Fm;   // the formulas read x, vimp and the (zero) column offset only
-            Fm.q = 0;
+            typename Slv::FS Fm;   // the formulas read x, vimp and the column offset only (zero
+            Fm.q = 0;              // but for the case-4 instances, N >= 7)
             Fm.xo2 = 0;
+            if constexpr (N >= 7) Fm.xo2 = S1.n_extra;
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 Fm.x[j] = P.x[j];
@@ -3884,6 +3903,7 @@ DCOL_HD void solve_stream(const KArgs& A, int64_t pi, int lane, typename StreamS
                     typename Slv::FS Fm;
                     Fm.q = 0;
                     Fm.xo2 = 0;
+                    if constexpr (N >= 7) Fm.xo2 = S1.n_extra;
 #pragma unroll
                     for (int j = 0; j < N; ++j) Fm.x[j] = P.x[j];
 #pragma unroll 1

@@ -200,6 +200,15 @@ inline bool stream_built(int N, int nsoc) {
     return false;
 }
 
+// ... or a case-4 instance (DCOL_STREAM_CASE4_SHAPES; routed only under DCOL_PLAN_CASE4_STREAM)
+inline bool stream_case4_built(int N, int nsoc) {
+#define DCOL_SB4(NN, NS) \
+    if (NN == N && NS == nsoc) return true;
+    DCOL_STREAM_CASE4_SHAPES(DCOL_SB4)
+#undef DCOL_SB4
+    return false;
+}
+
 // DCOL_NO_PART=1: no row-partitioned kernels (A/B runs, tests)
 inline bool part_disabled() {
     static const bool off = std::getenv("DCOL_NO_PART") != nullptr;
@@ -284,9 +293,11 @@ inline bool part_bucket(int N, int nsoc, int op, int oe, PairClass& c) {
 // stream: a pair of cases 1-3 with more rows than its (N, NSOC) bucket list holds, up to
 // DCOL_MAX_PAIR_ROWS, is OK and marked streamed (false: DCOL_TOO_LARGE, as for the contact-point
 // Jacobian's plans made without DCOL_PLAN_JACOBIAN_STREAM).  A pair that fits a bucket keeps it; a
-// case-4 pair (both primitives with extra columns) above its list stays DCOL_TOO_LARGE.
+// case-4 pair (both primitives with extra columns) above its list stays DCOL_TOO_LARGE, unless
+// case4_stream (DCOL_PLAN_CASE4_STREAM, with case4 and stream): then it is OK and marked streamed
+// when it has at most DCOL_MAX_PAIR_ROWS rows and its (N, NSOC) is in DCOL_STREAM_CASE4_SHAPES.
 inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = false, bool part = !part_disabled(),
-                          bool stream = true) {
+                          bool stream = true, bool case4_stream = false) {
     PairClass c{DCOL_OK, 4, 0, 0, 0, 0};
     if (a.n_extra > 0 && b.n_extra > 0 && !case4) {   // combine_problem_matrices.py:58-67 (case 4)
         c.status = DCOL_UNSUPPORTED;
@@ -307,7 +318,9 @@ inline PairClass classify(const DevShape& a, const DevShape& b, bool case4 = fal
                 c.lpp = choose_lpp(c.N, c.nsoc, om);
                 return c;
             }
-    if (stream && !(a.n_extra > 0 && b.n_extra > 0) && c.o <= DCOL_MAX_PAIR_ROWS && stream_built(c.N, c.nsoc)) {
+    const bool both = a.n_extra > 0 && b.n_extra > 0;
+    if (stream && c.o <= DCOL_MAX_PAIR_ROWS &&
+        (both ? (case4_stream && stream_case4_built(c.N, c.nsoc)) : stream_built(c.N, c.nsoc))) {
         c.stream = true;
         c.omax = DCOL_MAX_PAIR_ROWS;
         c.lpp = 64;

@@ -50,6 +50,11 @@ hipError_t launch_stream(int N, int nsoc, const KArgs& args, hipStream_t stream)
 // their contact-point Jacobian copies (dcol_kernels_stream_jac.hip): the same grid, for a run
 // with DCOL_JACOBIAN of a plan made with DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM
 hipError_t launch_stream_jac(int N, int nsoc, const KArgs& args, hipStream_t stream);
+// the case-4 streamed instances (dcol_kernels_stream_c4.hip, dcol_kernels_stream_c4_jac.hip;
+// DCOL_STREAM_CASE4_SHAPES): the same grid, for the streamed (7, 2) / (8, 2) buckets of a plan
+// made with DCOL_PLAN_CASE4 | DCOL_PLAN_CASE4_STREAM
+hipError_t launch_stream_c4(int N, int nsoc, const KArgs& args, hipStream_t stream);
+hipError_t launch_stream_c4_jac(int N, int nsoc, const KArgs& args, hipStream_t stream);
 
 // the contact-point Jacobian copies (dcol_kernels_jac.hip, one object per N): the dense-row
 // kernel of shape (N, nsoc, omax) at its DCOL_JAC_VARIANTS lanes per pair
@@ -125,7 +130,7 @@ hipError_t launch_pair_server(const KArgs& args, PairBox* box, int64_t idle_tick
         return v;                                                                              \
     }
 #define DCOL_EXEC_TAGS(X) X(n4) X(n5) X(n6) X(n7) X(n8) X(fused) X(packed) X(p51) X(p52) X(p61) X(p62) X(p62d) X(susp) X(server) X(stream) \
-    X(stream_jac) X(jac4) X(jac5) X(jac6) X(jac7) X(jac8)
+    X(stream_jac) X(stream_c4) X(stream_c4_jac) X(jac4) X(jac5) X(jac6) X(jac7) X(jac8)
 #define DCOL_EXEC_DECL(tag) unsigned long long exec_violations_##tag(bool reset);
 DCOL_EXEC_TAGS(DCOL_EXEC_DECL)
 DCOL_EXEC_DECL(capi)   // the C-ABI unit's own counter (dcol_debug_exec_selftest)

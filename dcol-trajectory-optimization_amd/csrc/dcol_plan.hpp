@@ -204,6 +204,10 @@ struct BucketMode {
     // to DCOL_MAX_PAIR_ROWS rows, are classified streamed as in a plain plan and run the
     // streamed kernels' Jacobian copies; without it they stay DCOL_TOO_LARGE
     bool jac_stream = false;
+    // DCOL_PLAN_CASE4_STREAM (with case4): case-4 pairs above their register buckets, up to
+    // DCOL_MAX_PAIR_ROWS rows, are classified streamed (classify's case4_stream) and get a
+    // streamed bucket per (7, 2) / (8, 2); in a Jacobian plan only with jac_stream as well
+    bool case4_stream = false;
 };
 
 // A launch too small to fill the GPU runs the configuration with the shortest per-pair
@@ -305,8 +309,8 @@ inline int bucket_pairs(const std::vector<DevShape>& shapes, int simds, int64_t 
         const DevShape& b = shapes[i2];
         // (a Jacobian plan's pairs above the buckets stay DCOL_TOO_LARGE unless it opted into
         // the streamed Jacobian copies: BucketMode::jac_stream)
-        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false, /*stream=*/mode.jac_stream)
-                               : classify(a, b, mode.case4);
+        PairClass c = mode.jac ? classify(a, b, mode.case4, /*part=*/false, /*stream=*/mode.jac_stream, mode.case4_stream)
+                               : classify(a, b, mode.case4, !part_disabled(), /*stream=*/true, mode.case4_stream);
         if (mode.jac && c.status == DCOL_OK && !c.stream) c.lpp = jac_lpp(c.N, c.nsoc, c.omax);
         const bool none_cone = a.soc_kind != SOC_CONE && b.soc_kind != SOC_CONE;
         const bool all_cone = a.soc_kind != SOC_BALL && b.soc_kind != SOC_BALL;
@@ -498,10 +502,13 @@ inline void plan_pack(PlanLayout& p, int simds, const PlanPolicy& pol) {
 // The layout of the plan of pairs (s1[i], s2[i]), i < B, over `shapes` on a device with
 // `simds` SIMDs.  allow_fuse = false (DCOL_PLAN_NO_FUSE): one launch per bucket.  Returns
 // DCOL_SUCCESS, or an error with last_error() set.
+// case4_stream (DCOL_PLAN_CASE4_STREAM, with case4): BucketMode::case4_stream.
 inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B, const int32_t* s1,
-                       const int32_t* s2, bool case4, bool allow_fuse, const PlanPolicy& pol, PlanLayout& out) {
+                       const int32_t* s2, bool case4, bool allow_fuse, const PlanPolicy& pol, PlanLayout& out,
+                       bool case4_stream = false) {
     BucketMode mode;
     mode.case4 = case4;
+    mode.case4_stream = case4 && case4_stream;
     int rc = bucket_pairs(shapes, simds, B, s1, s2, mode, pol, out);
     if (rc != DCOL_SUCCESS) return rc;
     // a plan that cannot fill the GPU: no one-lane row-partitioned buckets (BucketMode::lat_part)
@@ -543,6 +550,7 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
     if (allow_fuse && out.small && !out.fused() && !lpp_forced() && !pol.small_fanout) {
         BucketMode large;
         large.case4 = case4;
+        large.case4_stream = mode.case4_stream;
         large.force_large = true;
         PlanLayout q;
         if (bucket_pairs(shapes, simds, B, s1, s2, large, pol, q) == DCOL_SUCCESS) {
@@ -574,9 +582,11 @@ inline int plan_layout(const std::vector<DevShape>& shapes, int simds, int64_t B
 // by bucket_cost's streamed branch, spread over the streams with the other buckets -- and
 // the pairs of at most 128 rows the dense buckets they get without it.
 inline int plan_layout_jac(const std::vector<DevShape>& shapes, int simds, int64_t B, const int32_t* s1,
-                           const int32_t* s2, bool case4, const PlanPolicy& pol, PlanLayout& out, bool stream = false) {
+                           const int32_t* s2, bool case4, const PlanPolicy& pol, PlanLayout& out, bool stream = false,
+                           bool case4_stream = false) {
     BucketMode mode;
     mode.case4 = case4;
+    mode.case4_stream = case4 && case4_stream;   // (streamed only with `stream` too: classify)
     mode.force_large = true;
     mode.jac = true;
     mode.jac_stream = stream;

@@ -20,10 +20,12 @@ OK, MAXITER, UNSUPPORTED, NOT_PD, NONFINITE, TOO_LARGE = range(6)
 # enum dcol_flags
 GRAD_FD, GRAD_ENVELOPE, CONTACT, CASE4, GRAD_IMPLICIT, NO_GATHER, JACOBIAN = 1, 2, 4, 8, 16, 32, 64
 JACOBIAN_STREAM = 128   # dcol_prox_jacobian_host only: the streamed Jacobian copies (pairs of 129-1,024 rows)
+CASE4_STREAM = 256      # the host calls and dcol_prox_pair only: case-4 pairs of 33-1,024 rows (implies CASE4)
 GRAD_ANY = GRAD_FD | GRAD_ENVELOPE | GRAD_IMPLICIT
 # enum dcol_plan_options
 PLAN_CASE4, PLAN_NO_FUSE, PLAN_SUSPEND, PLAN_JACOBIAN = 1, 2, 4, 8
 PLAN_JACOBIAN_STREAM = 16   # only with PLAN_JACOBIAN
+PLAN_CASE4_STREAM = 32      # only with PLAN_CASE4
 SUCCESS, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3
 ABI_VERSION = 5
 PAIR_PLANS_MAX = 64   # DCOL_PAIR_PLANS_MAX

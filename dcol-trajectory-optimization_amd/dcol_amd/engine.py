@@ -61,7 +61,8 @@ def raise_for_status(status: int):
         raise ValueError("array must not contain infs or NaNs")                  # scipy check_finite
     if status == _lib.TOO_LARGE:
         raise ValueError(f"pair exceeds the engine's orthant-row capacity ({_lib.MAX_PAIR_ROWS} rows for the two primitives "
-                         "together; 32 for a case-4 pair, 128 with the contact-point Jacobian)")
+                         "together; 32 for a case-4 pair unless case4='stream' (DCOL_PLAN_CASE4_STREAM), "
+                         "128 with the contact-point Jacobian)")
     raise RuntimeError(f"unknown dcol status {status}")
 
 
@@ -117,13 +118,28 @@ def jacobian_mode(jacobian):
     return bool(jacobian)
 
 
+def case4_mode(case4):
+    """The case4= argument of Plan / Engine.plan / Engine.solve_host / Engine.solve_objects:
+    False, True (the DCOL_PLAN_CASE4 extension: case-4 pairs of at most 32 orthant rows) or
+    "stream" (also case-4 pairs of 33 to 1,024 rows, on the streamed-row kernels:
+    DCOL_PLAN_CASE4_STREAM) -> False, True or "stream"."""
+    if isinstance(case4, str):
+        if case4 != "stream":
+            raise ValueError(f"case4 must be False, True or 'stream', not {case4!r}")
+        return "stream"
+    return bool(case4)
+
+
 class Plan:
     """Owning wrapper of a dcol_plan: a fixed pairing bucketed by kernel variant."""
 
-    def __init__(self, table: Table, s1, s2, case4: bool = False, fuse: bool = True, suspend: bool = False,
+    def __init__(self, table: Table, s1, s2, case4=False, fuse: bool = True, suspend: bool = False,
                  jacobian=False):
         """case4=True: solve case-4 pairs (DCOL_PLAN_CASE4 extension) instead of reporting
-        UNSUPPORTED like the reference.  fuse=False: one launch per variant bucket even for
+        UNSUPPORTED like the reference; those above 32 orthant rows are TOO_LARGE.
+        case4="stream": the same plus DCOL_PLAN_CASE4_STREAM -- case-4 pairs of 33 to 1,024 rows
+        get a streamed bucket (self.case4 == "stream"; their Jacobian needs jacobian="stream"
+        too).  fuse=False: one launch per variant bucket even for
         a small mixed plan (DCOL_PLAN_NO_FUSE; A/B and tests).  suspend=True: large buckets
         run as a suspend / resume launch pair (DCOL_PLAN_SUSPEND; bitwise the same results;
         the plan owns scratch -- do not run it on two streams at once).  jacobian=True: the plan
@@ -139,9 +155,10 @@ class Plan:
         self.table = table
         self.B = int(self.s1.size)
         h = ctypes.c_void_p()
-        self.case4 = bool(case4)
+        self.case4 = case4_mode(case4)
         self.jacobian = jacobian_mode(jacobian)
-        opts = (_lib.PLAN_CASE4 if case4 else 0) | (0 if fuse else _lib.PLAN_NO_FUSE) | (
+        opts = (_lib.PLAN_CASE4 if self.case4 else 0) | (_lib.PLAN_CASE4_STREAM if self.case4 == "stream" else 0) | (
+            0 if fuse else _lib.PLAN_NO_FUSE) | (
             _lib.PLAN_SUSPEND if suspend else 0) | (_lib.PLAN_JACOBIAN if self.jacobian else 0) | (
             _lib.PLAN_JACOBIAN_STREAM if self.jacobian == "stream" else 0)
         _lib.check(lib.dcol_plan_create_ex(table.handle, self.B, _np_ptr(self.s1), _np_ptr(self.s2),
@@ -348,7 +365,7 @@ class Engine:
         s2 = np.ascontiguousarray(s2, dtype=np.int32)
         if not cache or suspend:   # suspend plans own scratch: never shared through the cache
             return Plan(self.table, s1, s2, case4, fuse, suspend, jacobian)
-        key = (s1.tobytes(), s2.tobytes(), bool(case4), bool(fuse), jacobian_mode(jacobian))
+        key = (s1.tobytes(), s2.tobytes(), case4_mode(case4), bool(fuse), jacobian_mode(jacobian))
         with self._lock:
             p = self._plans.get(key)
             if p is None or p.table is not self.table:
@@ -364,7 +381,8 @@ class Engine:
     def solve_host(self, s1, s2, pose1, pose2, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, grad="fd",
                    contact=True, case4=False, jacobian=False) -> Result:
         """Host arrays in/out: s1, s2 int [B]; pose1, pose2 float64 [B, 6] (r, p).
-        case4=True: the DCOL_CASE4 extension (see Plan).  jacobian=True: also Result.jac,
+        case4=True: the DCOL_CASE4 extension (see Plan); case4="stream": DCOL_CASE4_STREAM, case-4
+        pairs of 33 to 1,024 rows too.  jacobian=True: also Result.jac,
         (B, 4, 12), the contact-point Jacobian (dcol_prox_jacobian_host); pairs above 128
         orthant rows are TOO_LARGE then.  jacobian="stream": with DCOL_JACOBIAN_STREAM, pairs
         of 129 to 1,024 rows get their Jacobian from the streamed-row kernels."""
@@ -373,7 +391,9 @@ class Engine:
         B = s1.size
         p1 = np.ascontiguousarray(pose1, dtype=np.float64).reshape(B, 6)
         p2 = np.ascontiguousarray(pose2, dtype=np.float64).reshape(B, 6)
-        flags = grad_flag(grad) | (_lib.CONTACT if contact else 0) | (_lib.CASE4 if case4 else 0)
+        case4 = case4_mode(case4)
+        flags = grad_flag(grad) | (_lib.CONTACT if contact else 0) | (_lib.CASE4 if case4 else 0) | (
+            _lib.CASE4_STREAM if case4 == "stream" else 0)
         jacobian = jacobian_mode(jacobian)
         if jacobian == "stream":
             flags |= _lib.JACOBIAN_STREAM

@@ -46,7 +46,8 @@ extern "C" {
                                 5: the contact-point Jacobian: DCOL_PLAN_JACOBIAN, DCOL_JACOBIAN,
                                    dcol_plan_run_jac, dcol_prox_jacobian_host
                                    (additive since, same number: DCOL_MAX_PAIR_ROWS;
-                                   DCOL_PLAN_JACOBIAN_STREAM, DCOL_JACOBIAN_STREAM -- a library
+                                   DCOL_PLAN_JACOBIAN_STREAM, DCOL_JACOBIAN_STREAM;
+                                   DCOL_PLAN_CASE4_STREAM, DCOL_CASE4_STREAM -- a library
                                    from before them answers DCOL_ERR_ARG "unknown option bits") */
 
 /* Primitive types (misc_primitive_constructor.py:4-88). */
@@ -67,11 +68,12 @@ enum dcol_status {
     DCOL_NOT_PD = 3,      /* Cholesky of G'G or of the NT normal matrix failed            */
     DCOL_NONFINITE = 4,   /* a non-finite value reached a factorisation                   */
     DCOL_TOO_LARGE = 5    /* more orthant rows than the engine's row capacity: DCOL_MAX_PAIR_ROWS
-                             for a pair of combine cases 1-3; 32 for a case-4 pair (DCOL_PLAN_CASE4);
-                             128 in a DCOL_PLAN_JACOBIAN plan and dcol_prox_jacobian_host, unless
-                             they opt into the streamed Jacobian copies
+                             for a pair of combine cases 1-3; 32 for a case-4 pair (DCOL_PLAN_CASE4),
+                             DCOL_MAX_PAIR_ROWS with DCOL_PLAN_CASE4_STREAM / DCOL_CASE4_STREAM as
+                             well; 128 in a DCOL_PLAN_JACOBIAN plan and dcol_prox_jacobian_host,
+                             unless they opt into the streamed Jacobian copies
                              (DCOL_PLAN_JACOBIAN_STREAM / DCOL_JACOBIAN_STREAM): then
-                             DCOL_MAX_PAIR_ROWS for cases 1-3 there too                          */
+                             DCOL_MAX_PAIR_ROWS there too (case-4 pairs: with their own option) */
 };
 
 /* Orthant rows a pair's two primitives may bring together (polytope faces, polygon edges, the
@@ -105,11 +107,17 @@ enum dcol_flags {
                                contact-point Jacobian d[x0,x1,x2,alpha] / d[r1,p1,r2,p2]
                                (DifferentiableCollisions.jl proximity_jacobian; see
                                dcol_plan_run_jac).  Independent of the gradient flags.      */
-    DCOL_JACOBIAN_STREAM = 128 /* dcol_prox_jacobian_host only (as DCOL_CASE4 is for the batch
+    DCOL_JACOBIAN_STREAM = 128, /* dcol_prox_jacobian_host only (as DCOL_CASE4 is for the batch
                                host call): the transient plan is made with
                                DCOL_PLAN_JACOBIAN | DCOL_PLAN_JACOBIAN_STREAM, so pairs of 129
                                to DCOL_MAX_PAIR_ROWS rows get their Jacobian instead of
                                DCOL_TOO_LARGE.  Without it the call is unchanged.            */
+    DCOL_CASE4_STREAM = 256 /* dcol_prox_batch_host, dcol_prox_jacobian_host and dcol_prox_pair
+                               only: the transient (one-pair: cached) plan is made with
+                               DCOL_PLAN_CASE4 | DCOL_PLAN_CASE4_STREAM, so case-4 pairs of 33 to
+                               DCOL_MAX_PAIR_ROWS rows are solved instead of reported
+                               DCOL_TOO_LARGE.  Implies DCOL_CASE4.  Their Jacobian needs
+                               DCOL_JACOBIAN_STREAM as well.  Without it the calls are unchanged. */
 };
 #define DCOL_GRAD_ANY (DCOL_GRAD_FD | DCOL_GRAD_ENVELOPE | DCOL_GRAD_IMPLICIT)
 
@@ -138,7 +146,7 @@ enum dcol_plan_options {
                            launch, no suspend / resume, no order hint.  Not with
                            DCOL_PLAN_SUSPEND (DCOL_ERR_ARG).  Pairs above 128 rows get
                            DCOL_TOO_LARGE unless DCOL_PLAN_JACOBIAN_STREAM is set too.      */
-    DCOL_PLAN_JACOBIAN_STREAM = 16 /* only together with DCOL_PLAN_JACOBIAN (alone: DCOL_ERR_ARG):
+    DCOL_PLAN_JACOBIAN_STREAM = 16, /* only together with DCOL_PLAN_JACOBIAN (alone: DCOL_ERR_ARG):
                            pairs of combine cases 1-3 with 129 to DCOL_MAX_PAIR_ROWS orthant rows
                            get a streamed bucket per (N, NSOC), as in a plain plan (one wave per
                            slot, slots in descending row count), and dcol_plan_run_jac with
@@ -147,9 +155,21 @@ enum dcol_plan_options {
                            streamed kernels.  Either way alpha, contact, grad, iters and status
                            of those pairs are bitwise what a plain plan returns.  Pairs of at
                            most 128 rows keep their dense Jacobian bucket; pairs above
-                           DCOL_MAX_PAIR_ROWS rows and case-4 pairs above 32 keep
-                           DCOL_TOO_LARGE.  The Jacobian phase adds about six passes over the
+                           DCOL_MAX_PAIR_ROWS rows, and case-4 pairs above 32 in a plan without
+                           DCOL_PLAN_CASE4_STREAM, keep DCOL_TOO_LARGE.  The Jacobian phase adds about six passes over the
                            rows to a solve of about five per iteration. */
+    DCOL_PLAN_CASE4_STREAM = 32 /* only together with DCOL_PLAN_CASE4 (alone: DCOL_ERR_ARG): case-4
+                           pairs with more rows than the extension's register kernels hold (32),
+                           up to DCOL_MAX_PAIR_ROWS -- polygon x capsule / cylinder / polygon --
+                           get a streamed bucket per (N, NSOC) = (7, 2) / (8, 2): one wave per
+                           slot, slots in descending row count, and the plan takes the
+                           DCOL_FORM_BUCKETS form, as every plan with a streamed bucket.  Pairs of
+                           at most 32 rows keep their register bucket and are bitwise what a
+                           DCOL_PLAN_CASE4 plan returns.  In a DCOL_PLAN_JACOBIAN plan those
+                           pairs are streamed (and get their 48 entries, under the two NaN rules
+                           of dcol_plan_run_jac) only with DCOL_PLAN_JACOBIAN_STREAM as well;
+                           else they keep DCOL_TOO_LARGE.  Without the option nothing changes:
+                           such a pair is DCOL_TOO_LARGE.                                      */
 };
 
 /* Return codes of every entry point. */
@@ -206,7 +226,8 @@ int dcol_plan_num_buckets(const dcol_plan* plan, int32_t* n);  /* variant bucket
  * dcol_plan_num_streams streams), DCOL_FORM_FUSED one fused launch (a small plan: latency
  * configurations), DCOL_FORM_PACKED one packed launch (a mid-size plan: throughput
  * configurations).  A plan with a streamed bucket -- pairs of 129 to
- * DCOL_MAX_PAIR_ROWS orthant rows; dcol_plan_bucket reports it with [3] = DCOL_MAX_PAIR_ROWS and
+ * DCOL_MAX_PAIR_ROWS orthant rows, case-4 pairs of 33 to DCOL_MAX_PAIR_ROWS under
+ * DCOL_PLAN_CASE4_STREAM; dcol_plan_bucket reports it with [3] = DCOL_MAX_PAIR_ROWS and
  * [4] = 64 lanes per pair, its slots in descending row count -- always takes
  * DCOL_FORM_BUCKETS.                                                                       */
 enum dcol_plan_form { DCOL_FORM_BUCKETS = 0, DCOL_FORM_FUSED = 1, DCOL_FORM_PACKED = 2 };

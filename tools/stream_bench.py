@@ -15,7 +15,11 @@ line: ms per step, pair-solves/s, mean iterations, ns per pair x row x iteration
 rows for (6, 1), each in ONE plan made with jacobian="stream"; per round the FD-only run (the
 plain streamed kernels) and the run with the Jacobian (their JAC copies, FD gradient too)
 alternate.  Per batch one JSON line: ms per step of both and their ratio (of the minima).
-Usage: python3 tools/stream_bench.py [--pairs 4096] [--steps 30] [--rounds 4] [--jacobian]
+--case4: instead, the case-4 streamed kernels (csrc/dcol_kernels_stream_c4.hip; plans made with
+case4="stream"): polygon x polygon (8, 2) and cylinder x polygon (7, 2) batches at 40, 129, 512
+and 1,024 rows, and beside each the existing streamed (6, 2) instance (polygon x sphere) at the
+same row count -- the nearest kernel of cases 1-3 -- in the same session.
+Usage: python3 tools/stream_bench.py [--pairs 4096] [--steps 30] [--rounds 4] [--jacobian | --case4]
 """
 import argparse
 import json
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--check", type=int, default=64)
     ap.add_argument("--jacobian", action="store_true")
+    ap.add_argument("--case4", action="store_true")
     args = ap.parse_args()
     import torch
     from dcol_amd import Engine, ShapeSpec, alloc_outputs
@@ -55,11 +60,19 @@ def main():
         return ShapeSpec(5, A=tuple(A.reshape(-1)), b=tuple(b), R=0.2), O.ShapeSpec(O.POLYGON, A=A, b=b, R=0.2), k
 
     cone = (ShapeSpec(2, H=1.2, beta=0.4), O.ShapeSpec(O.CONE, H=1.2, beta=0.4), 1)
+    sph = (ShapeSpec(1, R=0.5), O.ShapeSpec(O.SPHERE, R=0.5), 0)
+    cyl = (ShapeSpec(4, R=0.3, L=1.0), O.ShapeSpec(O.CYLINDER, R=0.3, L=1.0), 4)
 
     cases = [("poly x poly 128 (register bucket)", poly(64), poly(64)), ("poly x poly 129", poly(65), poly(64)),
              ("poly x poly 256", poly(128), poly(128)), ("poly x poly 512", poly(256), poly(256)),
              ("poly x poly 1024", poly(512), poly(512)), ("polygon x poly 256", gon(128), poly(128)),
              ("poly x cone 256", poly(255), cone)]
+    case4 = "stream" if args.case4 else False
+    if args.case4:
+        cases = []
+        for r in (40, 129, 512, 1024):
+            cases += [(f"polygon x polygon {r}", gon(r // 2), gon(r - r // 2)), (f"cylinder x polygon {r}", cyl, gon(r - 4)),
+                      (f"polygon x sphere {r} (streamed (6, 2))", gon(r), sph)]
     eng = Engine(device=0)
     dev = torch.device("cuda", 0)
     B = args.pairs
@@ -75,7 +88,7 @@ def main():
         p2 = np.hstack([rng.uniform(-3, 3, (B, 3)), rng.uniform(-1, 1, (B, 3))])
         runs.append(dict(name=name, a=a, b=b, ia=ia, ib=ib, p1=p1, p2=p2))
     for r in runs:   # (plans after every shape is registered: one table)
-        plan = eng.plan(np.full(B, r["ia"], np.int32), np.full(B, r["ib"], np.int32))
+        plan = eng.plan(np.full(B, r["ia"], np.int32), np.full(B, r["ib"], np.int32), case4=case4)
         d1 = torch.from_numpy(np.ascontiguousarray(r["p1"].T)).to(dev)
         d2 = torch.from_numpy(np.ascontiguousarray(r["p2"].T)).to(dev)
         out = alloc_outputs(B, dev, want_grad=True, want_contact=False)
@@ -88,7 +101,8 @@ def main():
         al = out["alpha"].cpu().numpy()
         n = min(args.check, B)
         for i in range(n):
-            ra = O.proximity(r["a"][1], r["p1"][i, :3], r["p1"][i, 3:], r["b"][1], r["p2"][i, :3], r["p2"][i, 3:])
+            ra = O.proximity(r["a"][1], r["p1"][i, :3], r["p1"][i, 3:], r["b"][1], r["p2"][i, :3], r["p2"][i, 3:],
+                             case4=bool(case4))
             assert st[i] == 0 and it[i] == ra[5] and abs(al[i] - ra[0]) <= 1e-6 * abs(ra[0]), (r["name"], i)
         r.update(plan=plan, step=step, keep=(d1, d2, out), iters=float(it[st == 0].mean()), ok=int((st == 0).sum()),
                  bucket=plan.buckets()[0], ms=[])
